@@ -1,8 +1,14 @@
 """Throughput bench for the unbiased L1-ball type quantizer (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+A plain run does what the headline figure needs and no more: inputs, the one-time output
+placement probe, W warmup steps, K timed steps, the outputs of the last timed step when
+--dump-outputs is given, and the result line.  --full adds everything else this file
+measures or checks, each in a run of its own after the timed steps: the CPU baseline with its
+bit-parity and NMSE sample, the other pipelines and the side lines (biased, EDEN, codec,
+QUIC-FL) under `pipelines`, and the RCCL reduce timed alone (N > 1).
 Without an external launcher, --gpus N > 1 starts the N rank processes itself (spawn_ranks:
 child processes with the launcher's environment, rank 0's JSON line forwarded, non-zero exit
 if any rank fails); under a launcher --gpus must equal WORLD_SIZE.
@@ -25,10 +31,14 @@ around its launches inside the timed region.  Algorithmic bytes follow SURVEY.md
 (0.5*d as 4-bit fields, 1*d as int8) is implementation traffic, reported apart (`impl_bytes_per_launch`) and never
 counted as achieved bandwidth; --pipeline encode (no q) counts 4*d.  `roofline.step` prices
 the whole step the same way (8*d per vector / ms_per_step) and sets the PMC traffic of all
-the step's kernels against it.  W warmup steps run first.  `cpu_baseline` times the C
+the step's kernels against it.  W warmup steps run first.  `cpu_baseline` (--full) times the C
 restatement of the reference path (oracle/, the checker) on this host: the whole batch
 with clients over all the host's allotted cores (OpenMP) and a bounded single-thread
 sample; the batch doubles as a bit-parity and NMSE check of the GPU output.
+
+--dump-outputs DIR writes what the last timed step left for its caller as DIR/<name>.npy
+(float32; see dump_outputs).  The inputs depend on the arguments only (seeded generators), so
+two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -83,6 +93,13 @@ def parse(argv=None):
     ap.add_argument("--side-pipelines", action="store_true", default=True,
                     help="also time the other pipelines (reported under 'pipelines')")
     ap.add_argument("--no-side-pipelines", dest="side_pipelines", action="store_false")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: the CPU baseline "
+                         "and parity sample (unless --no-cpu-baseline), the other pipelines and side lines (unless "
+                         "--no-side-pipelines), the RCCL reduce timed alone (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32; est, l1, kmax whole, "
+                         "a fixed seeded sample of q and of the type codes)")
     return ap.parse_args(argv)
 
 
@@ -305,8 +322,9 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    est_last = None
     for k in range(args.steps):
-        sh.step(x, X, events=evs[k], pipeline=args.pipeline)
+        est_last = sh.step(x, X, events=evs[k], pipeline=args.pipeline)
     sh.drain()                                    # every reduce inside the timed region
     torch.cuda.synchronize()
     if dist is not None:
@@ -314,12 +332,15 @@ def main():
     elapsed = time.perf_counter() - t0
     elapsed_local = elapsed
     pipe.check_status()                           # status after the timed steps
+    if args.dump_outputs:                         # before anything else touches the pipeline's buffers
+        dump_outputs(args.dump_outputs, pipe, est_last if rank == sh.dst else None, args.pipeline, args.seed,
+                     rank, world)
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if BACKEND == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     reduce_alone = None
-    if dist is not None and args.mean_mode == "reduce" and BACKEND == "nccl":
+    if args.full and dist is not None and args.mean_mode == "reduce" and BACKEND == "nccl":
         # the collective by itself (the timed steps overlap it, so their 'reduce' segment
         # only covers its enqueue): events around reduce + wait on the caller's stream
         ra = []
@@ -348,12 +369,12 @@ def main():
     traffic, traffic_src, step_traffic = load_traffic(args.traffic_json, d, n, args.pipeline)
     step_alg = float(d * n_total) * 8 / world      # quantize+dequantize bytes of one rank's clients
     step_achieved = step_alg / (ms_per_step * 1e-3) / 1e9
-    # CPU baseline + parity sample on the timed steps' own output q (before any side line)
+    # --full: CPU baseline + parity sample on the timed steps' own output q (before any side line)
     base = parity = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         base, parity = cpu_baseline(args, x, X_cpu, q, m, T)
     side = {}
-    if args.side_pipelines and world == 1:
+    if args.full and args.side_pipelines and world == 1:
         for pl in ("q", "codes", "encode", "codes4"):
             if pl != args.pipeline and (pl != "codes4" or uqdme.codes4_fits(n, d, args.bits)):
                 ms = time_pipeline(pl, max(3, args.steps // 2))
@@ -372,7 +393,7 @@ def main():
         result = {
             "metric": METRIC, "value": round(value, 6), "unit": "M-vectors/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "full": bool(args.full),
             "data": {"normal": "synthetic: i.i.d. N(0,1) f32 per client (torch CUDA generator)",
                      "laplace": "synthetic: i.i.d. Laplace(1,2) f32 per client (torch CUDA generator, inversion)",
                      "uniform": "synthetic: i.i.d. U(-1,1) f32 per client (torch CUDA generator)"}[args.dist]
@@ -421,6 +442,46 @@ def main():
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_SAMPLE = 1 << 22     # elements taken from each per-coordinate output (16 MB as float32)
+
+
+def dump_outputs(path, pipe, est, pipeline, seed, rank=0, world=1):
+    """--dump-outputs: what the last timed step left for its caller, as <path>/<name>.npy in
+    float32 (exact: f32 data, and codes and counts that stay far below 2^24 at d <= 2^24):
+        est           the client-ordered mean [d] (rank `dst` only when N > 1)
+        l1            the clients' L1 norms [n]
+        kmax          the clients' largest lattice count [n] (pipelines that write codes)
+        q_sample      DUMP_SAMPLE elements of the dequantized q [n, d] (all of it when smaller)
+        q_first       q of the rank's first client [d]
+        codes_sample  DUMP_SAMPLE elements of the code buffer as the kernel wrote it: int8 type
+                      codes [n, d], or for codes4 the bytes [n, d/2] that hold two 4-bit fields
+    The sample positions are drawn once from numpy's default_rng(seed) over the flat element
+    index, sorted: the same for every run with the same arguments (~40 MB in all at the
+    default shape).  With N > 1 every rank writes its own files, named <name>_rank<r>.npy."""
+    os.makedirs(path, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+
+    def sample(t):
+        rows, cols = t.shape
+        total = rows * cols
+        if total <= DUMP_SAMPLE:
+            return t
+        idx = np.sort(np.random.default_rng(seed).integers(0, total, size=DUMP_SAMPLE, dtype=np.int64))
+        idx = torch.from_numpy(idx).to(t.device)
+        return t[idx // cols, idx % cols]
+
+    out = {"l1": pipe.l1}
+    if est is not None:
+        out["est"] = est
+    if pipeline != "encode":
+        out["q_sample"], out["q_first"] = sample(pipe.q), pipe.q[0]
+    if pipeline != "q":
+        out["kmax"] = pipe.kmax
+        out["codes_sample"] = sample(pipe.nib if pipeline == "codes4" else pipe.codes)
+    for name, t in out.items():
+        np.save(os.path.join(path, f"{name}{sfx}.npy"), t.to(torch.float32).cpu().numpy())
 
 
 def time_biased(uqdme, x, bits, T, steps):

@@ -72,6 +72,47 @@ def test_spawn_ranks_fails_when_a_rank_fails(stub):
     assert rc == 1
 
 
+def test_plain_run_is_the_default():
+    args = bench.parse(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert args.full is False and args.dump_outputs is None and args.steps == 3 and args.warmup == 1
+    args = bench.parse(["--full", "--dump-outputs", "out"])
+    assert args.full is True and args.dump_outputs == "out"
+
+
+def test_dump_outputs_files(tmp_path, monkeypatch):
+    """--dump-outputs on a stand-in pipeline with host tensors: float32 files, small outputs
+    whole, large ones as the same seeded sample in every run."""
+    import types
+
+    import numpy as np
+    import torch
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 1000)
+    n, d = 8, 4096
+    g = torch.Generator().manual_seed(3)
+    q = torch.randn(n, d, generator=g)
+    pipe = types.SimpleNamespace(
+        q=q, l1=q.abs().sum(1), kmax=torch.arange(n, dtype=torch.int32), codes=None,
+        nib=torch.randint(0, 256, (n, d // 2), generator=g, dtype=torch.uint8))
+    est = q.mean(0)
+    for sub in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / sub), pipe, est, "codes4", 1234)
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == ["codes_sample.npy", "est.npy", "kmax.npy", "l1.npy", "q_first.npy", "q_sample.npy"]
+    for nm in names:
+        a, b = np.load(tmp_path / "a" / nm), np.load(tmp_path / "b" / nm)
+        assert a.dtype == np.float32 and np.array_equal(a, b), nm
+    assert np.array_equal(np.load(tmp_path / "a" / "est.npy"), est.numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "q_first.npy"), q[0].numpy())
+    idx = np.sort(np.random.default_rng(1234).integers(0, n * d, size=1000, dtype=np.int64))
+    assert np.array_equal(np.load(tmp_path / "a" / "q_sample.npy"), q.numpy().reshape(-1)[idx])
+    cs = np.load(tmp_path / "a" / "codes_sample.npy")
+    assert cs.shape == (1000,) and cs.min() >= 0 and cs.max() <= 255
+    # an encode-only step has no q; a q-only step no codes; ranks of a larger world name their files
+    bench.dump_outputs(str(tmp_path / "c"), pipe, None, "q", 1234, rank=1, world=2)
+    assert sorted(p.name for p in (tmp_path / "c").iterdir()) == ["l1_rank1.npy", "q_first_rank1.npy",
+                                                                 "q_sample_rank1.npy"]
+
+
 def test_world_must_match_gpus(monkeypatch):
     monkeypatch.setenv("WORLD_SIZE", "2")
     args = bench.parse(["--gpus", "8"])

@@ -5,7 +5,7 @@
 #   tests       all -m gpu tests               -> gpurun_out/<tag>/gputest.log
 #   tests:<f>   only tests/<f> (repeatable, e.g. tests:test_gpu_pipeline.py)
 #   smoke       __graft_entry__.smoke()       -> smoke.log
-#   bench       python bench.py               -> bench.json
+#   bench       python bench.py --full        -> bench.json
 #   gloo2       2-rank gloo rehearsal of bench.py --gpus 2 under torch.distributed.run (ranks share cuda:0)
 #   self2       the same, bench.py --gpus 2 starting its own ranks (no external launcher)
 #   dropin      tools/dropin_latency.py       -> dropin_latency.json
@@ -25,7 +25,7 @@ for s in $STEPS; do
                TESTS=""
              fi ;;
     smoke) timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 ;;
-    bench) timeout -k 10 300 python bench.py > $O/bench.json 2> $O/bench.err ;;
+    bench) timeout -k 10 300 python bench.py --full > $O/bench.json 2> $O/bench.err ;;
     gloo2) UQDME_BENCH_BACKEND=gloo timeout -k 10 240 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
              --master-addr 127.0.0.1 --master-port 29553 bench.py --gpus 2 --steps 5 --warmup 2 \
              > $O/bench_gloo2.json 2> $O/bench_gloo2.err ;;
