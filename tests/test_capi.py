@@ -224,3 +224,43 @@ def test_quicfl_workspaces_cover_the_jump_paths(lib):
     assert lib.uq_quicfl_receive_workspace_bytes(-1, 16, ctypes.byref(sz)) < 0
     assert lib.uq_rht_sign_bits(None, -1, 16, None, None) < 0
     assert lib.uq_rht_sign_bits(None, 0, 16, None, None) == 0        # nothing to pack
+
+
+def test_exported_symbols_are_the_c_api(lib):
+    """The library's defined dynamic symbols are the C API and nothing of its internals: every
+    one is a uq_* function, a libstdc++ template instance or a __hip_* object of the HIP
+    runtime's registration, and the uq_* set is the header's declarations plus
+    uq_mtpoly_progression (the jump polynomials' internal entry point in the host-only unit)."""
+    import subprocess
+    from uqdme_amd import build_ext
+    out = subprocess.run(["nm", "-D", "--defined-only", build_ext.SO], check=True, capture_output=True, text=True).stdout
+    syms = [line.split() for line in out.splitlines() if line.strip()]
+    assert syms
+    uq = set()
+    for *_, kind, name in syms:
+        if name.startswith("uq_"):
+            assert kind == "T", (name, kind)
+            uq.add(name)
+        else:
+            assert name.startswith(("_ZNSt", "_ZSt", "__hip_")), name
+    assert uq == set(declared_functions()) | {"uq_mtpoly_progression"}
+
+
+def test_last_error_crosses_translation_units(lib):
+    """One error string serves every part of the library: a host-only argument error in the
+    core, the biased quantizer, EDEN, QUIC-FL and the codec (one source file each) returns a
+    negative code, and uq_last_error() then holds that call's own message, not the one before."""
+    b = ctypes.c_size_t()
+    calls = (
+        (lambda: lib.uq_workspace_bytes(-1, 1000, 1, ctypes.byref(b)), b"bad n/d/torch_threads"),
+        (lambda: lib.uq_biased_workspace_bytes(4, 1000, 1, None), b"null bytes_out"),
+        (lambda: lib.uq_eden_workspace_bytes(-1, 16, ctypes.byref(b)), b"n and dim must be >= 0"),
+        (lambda: lib.uq_quicfl_receive_workspace_bytes(-1, 16, ctypes.byref(b)), b"n and D must be >= 0"),
+        (lambda: lib.uq_tc_bound(-1, ctypes.byref(b)), b"bad d / null bytes_out"),
+    )
+    prev = None
+    for call, expect in calls + calls[:1]:
+        assert call() < 0
+        msg = lib.uq_last_error()
+        assert msg and msg == expect and msg != prev
+        prev = msg

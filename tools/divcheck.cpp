@@ -1,4 +1,4 @@
-// Host check of the fast exact f32 division used on the GPU (uq_dme.hip div_rn):
+// Host check of the fast exact f32 division used on the GPU (csrc/uq_common.h, div1 / div4):
 // q64 = (double)a * RN64(1/(double)b); RN32(q64) unless q64 is within 2 ulp64 of an
 // f32 rounding midpoint or outside the f32 normal range, where a / b is used.
 // Compile: g++ -O2 -ffp-contract=off tools/divcheck.cpp -o /tmp/divcheck

@@ -4,9 +4,9 @@ K2 (q + codes, C2 batch) runs at ~1.67 ms or ~1.95 ms depending on where q and t
 land in physical memory.  Every one of the 1024 concurrent workgroups writes
 tile t of its row at the same offset inside its own 4 MiB q row (1 MiB codes row), so all
 concurrent writes share their low address bits and the channel mix is left to the
-physical frames.  The first run used a variant library
-taking the row pitches from constant memory (`build`); the product now takes them
-(uq_type_unbiased_codes_ld_f32), and `run` / `run2` time that:
+physical frames.  The first run used a variant library taking the row pitches from constant
+memory; the product now takes them (uq_type_unbiased_codes_ld_f32), and `run` / `run2` time
+that:
 
     python tools/exp/k2_pitch.py run|run2     (GPU box: JSON lines, one per config/sweep)
 
@@ -16,53 +16,9 @@ pages) and time K2 on every set; a config that is fast on every set removes the 
 import ctypes
 import json
 import os
-import shutil
-import subprocess
 import sys
-import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-PKG = os.path.join(ROOT, "unbiased-quantization-distributed-mean-estimation_amd")
-OUT = os.path.join(ROOT, "tools", "exp", "_pitch")
-SO = os.path.join(OUT, "libpitch.so")
-
-SUBS = [
-    ("const __amdgpu_buffer_rsrc_t ro = make_rsrc(WQ ? out + vec * d : x, row_bytes);",
-     "const __amdgpu_buffer_rsrc_t ro = make_rsrc(WQ ? out + vec * (g_ldo ? g_ldo : d) : x, row_bytes);"),
-    ("const __amdgpu_buffer_rsrc_t rc = make_rsrc(WC ? (const void*)(codes + vec * d) : (const void*)x, row_bytes / 4u);",
-     "const __amdgpu_buffer_rsrc_t rc = make_rsrc(WC ? (const void*)(codes + vec * (g_ldc ? g_ldc : d)) : (const void*)x, row_bytes / 4u);"),
-    ("template <bool WQ, bool WC, bool CVEC>\n__global__ void __launch_bounds__(kQBlock, 4)\nquantize_stream_kernel(",
-     "__constant__ int64_t g_ldo;\n__constant__ int64_t g_ldc;\ntemplate <bool WQ, bool WC, bool CVEC>\n"
-     "__global__ void __launch_bounds__(kQBlock, 4)\nquantize_stream_kernel("),
-]
-SETTER = """
-extern "C" int uq_exp_set_ld(int64_t ldo, int64_t ldc) {
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_ldo), &ldo, sizeof(ldo)) != hipSuccess) return -2;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_ldc), &ldc, sizeof(ldc)) != hipSuccess) return -2;
-    return 0;
-}
-"""
-
-
-def build():
-    sys.path.insert(0, PKG)
-    import build_ext as be
-    top = tempfile.mkdtemp(prefix="uq_pitch_")
-    d = os.path.join(top, "pkg", "csrc")
-    os.makedirs(d)
-    os.symlink(os.path.join(ROOT, "include"), os.path.join(top, "include"))
-    for f in os.listdir(os.path.join(PKG, "csrc")):
-        shutil.copy(os.path.join(PKG, "csrc", f), d)
-    src = os.path.join(d, "uq_dme.hip")
-    s = open(src).read()
-    for a, b in SUBS:
-        if s.count(a) != 1:
-            raise SystemExit(f"pattern found {s.count(a)} times: {a[:60]}")
-        s = s.replace(a, b)
-    open(src, "w").write(s + SETTER)
-    os.makedirs(OUT, exist_ok=True)
-    subprocess.run([be.hipcc(), *be.HIPCC_FLAGS, "-o", SO, src], check=True)
-    print("built", SO)
 
 
 # (name, extra q floats per row, extra code bytes per row, codes inside the q allocation)
@@ -164,4 +120,4 @@ if __name__ == "__main__":
     if sys.argv[1] == "run2":
         run(trials=5, configs=CONFIGS2)
     else:
-        {"build": build, "run": run}[sys.argv[1]]()
+        {"run": run}[sys.argv[1]]()

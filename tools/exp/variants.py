@@ -29,11 +29,6 @@ def build(spec_path):
     variants = json.load(open(spec_path))
     shutil.rmtree(OUT, ignore_errors=True)
     os.makedirs(OUT)
-    objs = []                                      # the tree's host code (no GPU work) in every variant
-    for f in be.HOST_SRCS:
-        objs.append(os.path.join(OUT, os.path.basename(f)[:-4] + ".o"))
-        subprocess.run(["g++", *be.HOST_FLAGS, "-c", "-o", objs[-1], f], check=True)
-    procs = []
     for name, subs in variants.items():
         top = os.path.join(OUT, name)
         src = os.path.join(top, "pkg", "csrc")
@@ -51,21 +46,13 @@ def build(spec_path):
         else:
             for f in os.listdir(os.path.join(PKG, "csrc")):
                 shutil.copy(os.path.join(PKG, "csrc", f), src)
-        for f in os.listdir(src):                  # host sources are linked from objs
-            if f.endswith(".cpp"):
-                os.remove(os.path.join(src, f))
         for fname, old, new in subs:
             p = os.path.join(src, fname)
             t = open(p).read()
             assert old in t, (name, fname, old[:60])
             open(p, "w").write(t.replace(old, new))
-        so = os.path.join(top, "libuq_dme.so")
-        procs.append((name, subprocess.Popen([be.hipcc(), *be.HIPCC_FLAGS, "-o", so, os.path.join(src, "uq_dme.hip"),
-                                              "-x", "none", *objs, "-lpthread"])))
-    bad = [n for n, p in procs if p.wait() != 0]
-    if bad:
-        raise SystemExit(f"variant builds failed: {bad}")
-    print("built", [n for n, _ in procs])
+        be.build(src_dir=src, out=os.path.join(top, "libuq_dme.so"))
+    print("built", list(variants))
 
 
 def run(name, tool, args):

@@ -1,5 +1,5 @@
 /* Exhaustive check of the division x / den in the stream and look-back kernels' pass 1
- * (csrc/uq_dme.hip: div_plan / div4).  Tool, not shipped.
+ * (csrc/uq_common.h: div_plan / div4).  Tool, not shipped.
  *
  *   den = L1 + 1e-12 (>= 2^-39.9);  fast path only while den < 2^40
  *   y   = RN(1/den)                              one IEEE division per client

@@ -11,13 +11,15 @@ import hashlib
 import os
 import subprocess
 import sys
+from concurrent.futures import ThreadPoolExecutor
+from typing import Sequence
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(PKG_DIR, "csrc", "uq_dme.hip")
-# host-only C++, g++, linked into the same library: the MT19937 jump polynomials, and numpy's
-# legacy RandomState samplers for the NMSE harness (uq_legacy_rng.cpp: -ffp-contract=off, every
-# product and sum rounded on its own as in numpy's baseline build; log/exp from the host libm)
-HOST_SRCS = [os.path.join(PKG_DIR, "csrc", f) for f in ("uq_mt_poly.cpp", "uq_legacy_rng.cpp")]
+# csrc/*.hip: one device translation unit per scheme (hipcc).  csrc/*.cpp: host-only C++ (g++)
+# linked into the same library: the MT19937 jump polynomials, and numpy's legacy RandomState
+# samplers for the NMSE harness (uq_legacy_rng.cpp: -ffp-contract=off, every product and sum
+# rounded on its own as in numpy's baseline build; log/exp from the host libm)
+CSRC = os.path.join(PKG_DIR, "csrc")
 OUT_DIR = os.path.join(PKG_DIR, "_build")
 SO = os.path.join(OUT_DIR, "libuq_dme.so")
 
@@ -51,9 +53,8 @@ def build_id() -> str:
     the identity of the binary they produce.  The library reports the id it was built from
     (uq_build_id), so a stale binary is detected by content, not by file times."""
     h = hashlib.sha256()
-    csrc = os.path.join(PKG_DIR, "csrc")
-    for f in sorted(os.listdir(csrc)) + [None]:
-        path = HEADER if f is None else os.path.join(csrc, f)
+    for f in sorted(os.listdir(CSRC)) + [None]:
+        path = HEADER if f is None else os.path.join(CSRC, f)
         h.update((os.path.basename(path) + "\0").encode())
         with open(path, "rb") as fh:
             h.update(fh.read())
@@ -68,23 +69,59 @@ def needs_build() -> bool:
         return f.read().strip() != build_id()
 
 
-def build(force: bool = False, verbose: bool = False) -> str:
-    if not force and not needs_build():
+def _jobs(n: int) -> int:
+    """Parallel compiles: one per translation unit, 16 at most, MAX_JOBS if set (never the CPU count)."""
+    try:
+        cap = int(os.environ.get("MAX_JOBS", ""))
+    except ValueError:
+        cap = 16
+    return max(1, min(16, cap, n))
+
+
+def build(force: bool = False, verbose: bool = False, src_dir: str = CSRC, out: str = SO,
+          extra_flags: Sequence[str] = ()) -> str:
+    """Compile every src_dir/*.hip (device translation units, hipcc) and src_dir/*.cpp (host,
+    g++) to objects, in parallel, and link them into `out`.  The defaults build the package's
+    library, and only those are skipped when the library on disk is current; another src_dir
+    (csrc/ of another revision, a patched copy), `out` or extra_flags (-D...) is what the
+    measurement tools use."""
+    default = src_dir == CSRC and out == SO and not extra_flags
+    if default and not force and not needs_build():
         return SO
-    os.makedirs(OUT_DIR, exist_ok=True)
+    obj_dir = out + ".obj"
+    os.makedirs(obj_dir, exist_ok=True)
     bid = build_id()
-    tmp = SO + ".tmp"
-    objs = [os.path.join(OUT_DIR, os.path.basename(f)[:-4] + ".o") for f in HOST_SRCS]
-    cmds = [[os.environ.get("CXX", "g++"), *HOST_FLAGS, "-c", "-o", o, f] for f, o in zip(HOST_SRCS, objs)]
-    cmds.append([hipcc(), *HIPCC_FLAGS, f'-DUQ_BUILD_ID="{bid}"', "-o", tmp, SRC, "-x", "none", *objs, "-lpthread"])
-    for cmd in cmds:
+    cmds, objs = [], []
+    for f in sorted(os.listdir(src_dir)):
+        path = os.path.join(src_dir, f)
+        obj = os.path.join(obj_dir, f + ".o")
+        if f.endswith(".hip"):
+            with open(path, "rb") as fh:
+                owns_id = b"UQ_BUILD_ID" in fh.read()      # the unit that defines uq_build_id
+            ident = [f'-DUQ_BUILD_ID="{bid}"'] if owns_id and default else []
+            cmds.append([hipcc(), *[x for x in HIPCC_FLAGS if x != "-shared"], *extra_flags, *ident, "-c", "-o", obj, path])
+        elif f.endswith(".cpp"):
+            cmds.append([os.environ.get("CXX", "g++"), *HOST_FLAGS, "-c", "-o", obj, path])
+        else:
+            continue
+        objs.append(obj)
+    if not any(o.endswith(".hip.o") for o in objs):
+        raise RuntimeError(f"no .hip source in {src_dir}")
+
+    def run(cmd):
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.run(cmd, check=True)
-    os.replace(tmp, SO)
-    with open(ID_FILE, "w") as f:
-        f.write(bid + "\n")
-    return SO
+
+    with ThreadPoolExecutor(_jobs(len(cmds))) as pool:
+        list(pool.map(run, cmds))
+    tmp = out + ".tmp"
+    run([hipcc(), *HIPCC_FLAGS, "-o", tmp, *objs, "-lpthread"])
+    os.replace(tmp, out)
+    if default:
+        with open(ID_FILE, "w") as f:
+            f.write(bid + "\n")
+    return out
 
 
 if __name__ == "__main__":

@@ -1,5 +1,5 @@
 // uq_biased_kernels.h — device code of the biased type quantizer (Reznik rounding).
-// Included by uq_dme.hip inside its anonymous namespace (shares the K1 cascade).
+// Included by uq_biased.hip.  Shares the K1 cascade (uq_common.h) with the unbiased quantizer.
 //
 // Reference (paths relative to the reference root):
 //   NMSE_Results/Codes/All_Schemes.py:669-687  Type_biased_quantize
@@ -24,6 +24,76 @@
 // When the threshold value occurs more often than it is selected ("ambiguous"), torch's
 // choice is the one libstdc++'s nth_element / partial_sort makes; KB6 takes the lowest
 // indices instead, and the torch choice is replayed by uq_biased_torch_ties.h.
+
+#ifndef UQ_BIASED_KERNELS_H
+#define UQ_BIASED_KERNELS_H
+
+#include "uq_common.h"
+
+namespace {
+
+// Element transforms of the K1 cascade (uq_common.h) for KB2: the cascade itself (order of
+// f32 adds) is the torch CPU `sum` order whatever is summed.
+struct RezKOp {           // AS:648-649  k' = floor(m * p + 0.5), p = |x| / (L1 + 1e-12)
+    DivPlan dp;
+    float fm;
+    uint32_t *h, *zn;
+    __device__ static RezKOp make(const float* l1, float fm, int64_t vec) {
+        return RezKOp{div_plan(l1[vec]), fm, nullptr, nullptr};
+    }
+    __device__ float operator()(float v) const { return floorf(fm * div1(fabsf(v), dp) + 0.5f); }
+    // four elements per call (K1a): the quotients by div4 (one underflow test per four,
+    // the same bits as div1), then the per-element op; a[c] += op(v[c]) in the same order
+    __device__ void apply4(const float (&v)[4], float (&a)[4]) const {
+        const float ab[4] = {fabsf(v[0]), fabsf(v[1]), fabsf(v[2]), fabsf(v[3])};
+        float qs[4];
+        div4(ab, dp, qs);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) a[c] += floorf(fm * qs[c] + 0.5f);
+    }
+};
+// The fine bin of a selection value v: non-decreasing in v (so in the key), 2^11 bins linear
+// in |v| (delta' lies in [-0.5, 0.5]): v > 0 -> 1024 + min(1023, floor(2048 |v|)), v < 0 ->
+// 1023 - min(1023, floor(2048 |v|)), +-0 -> 1024, NaN -> 2047 (ATen's topk puts NaN first).
+// For v != 0 and not NaN, fbin(-v) = 2047 - fbin(v): KB2 counts +delta' and KB4a mirrors the
+// counts for Delta < 0, moving zeros (1023 -> 1024) and NaNs (0 -> 2047) back.
+__device__ __forceinline__ uint32_t rez_fbin(float v) {
+    if (v != v) return 2047u;
+    const float a = fabsf(v) * 2048.0f;                   // exact (a power-of-two scale)
+    const uint32_t q = a >= 1023.0f ? 1023u : (uint32_t)a;
+    return v > 0.f ? 1024u + q : (v < 0.f ? 1023u - q : 1024u);
+}
+
+// RezKOp that also counts the fine bin (rez_fbin) of +delta' = k' - m p into h[2048] (KB4a's
+// histogram), and delta' == 0 / NaN elements into zn[0] / zn[1] so that the histogram of
+// -delta' can be mirrored from it.
+// h / zn point to LDS in K1a (flushed per workgroup) and to global memory in K1b.
+struct RezKHistOp {
+    static constexpr bool kHist = true;
+    DivPlan dp;
+    float fm;
+    uint32_t *h, *zn;
+    __device__ static RezKHistOp make(const float* l1, float fm, int64_t vec) {
+        return RezKHistOp{div_plan(l1[vec]), fm, nullptr, nullptr};
+    }
+    __device__ float count(float mp) const {
+        const float kp = floorf(mp + 0.5f);
+        const float dp = (kp - mp) + 0.0f;                 // the value rez_key_of(dp, true) encodes
+        atomicAdd(&h[rez_fbin(dp)], 1u);
+        if (dp == 0.0f) atomicAdd(&zn[0], 1u);
+        else if (dp != dp) atomicAdd(&zn[1], 1u);
+        return kp;
+    }
+    __device__ float operator()(float v) const { return count(fm * div1(fabsf(v), dp)); }
+    __device__ void apply4(const float (&v)[4], float (&a)[4]) const {     // as RezKOp::apply4
+        const float ab[4] = {fabsf(v[0]), fabsf(v[1]), fabsf(v[2]), fabsf(v[3])};
+        float qs[4];
+        div4(ab, dp, qs);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) a[c] += count(fm * qs[c]);
+    }
+};
+
 
 constexpr int kRadixBins = 2048;
 constexpr int kHistItems = 64;                      // elements per thread in a histogram pass
@@ -940,3 +1010,7 @@ biased_small_kernel(const float* __restrict__ x, float* __restrict__ out, int64_
         st[vec] = s;
     }
 }
+
+}  // namespace
+
+#endif  // UQ_BIASED_KERNELS_H

@@ -1,5 +1,5 @@
 // uq_biased_torch_ties.h — KB7: replay torch CPU's topk tie choice for ambiguous clients.
-// Included by uq_dme.hip after uq_biased_kernels.h (anonymous namespace).
+// Included by uq_biased.hip.
 //
 // torch.topk on a CPU f32 vector (ATen TopKImpl.h; torch is built against libstdc++)
 // fills a queue of (value, index) pairs in index order and runs
@@ -23,6 +23,13 @@
 // Each workgroup owns one scratch slot (keys[d], indices[d] = the queue in SoA form, plus
 // two position lists) and walks the clients blockIdx.x, +gridDim.x, ...; clients without
 // an ambiguous tie are skipped.  Ranges of <= kTieLdsPairs finish in LDS.
+
+#ifndef UQ_BIASED_TORCH_TIES_H
+#define UQ_BIASED_TORCH_TIES_H
+
+#include "uq_biased_kernels.h"
+
+namespace {
 
 constexpr int kTieSlots = 256;       // workgroups (and scratch slots) of KB7: one per CU
 constexpr int kTieThreads = 1024;    // 16 waves per client (full replays)
@@ -1189,3 +1196,7 @@ rez_ties_kernel(const float* __restrict__ x, int64_t d, const float* __restrict_
         __syncthreads();
     }
 }
+
+}  // namespace
+
+#endif  // UQ_BIASED_TORCH_TIES_H

@@ -1,5 +1,5 @@
 // Type-message codec "UQR1": rANS over the int8 type codes.
-// Included by uq_dme.hip inside its anonymous namespace.  Format and symbol map: see the
+// Included by uq_codec.hip.  Format and symbol map: see the
 // header of include/uq_dme.h (uq_tc_*) and codes.py; oracle/uq_codec.c restates it on the CPU
 // byte for byte (tests compare whole messages).
 //
@@ -19,6 +19,15 @@
 //                          exactly
 // Bytes: KC1 and KC3 read the codes (d per client each), KC3 writes <= 2 B per symbol of
 // scratch, KC6 copies the words; KC7 reads the message and writes d code bytes.
+#ifndef UQ_CODEC_KERNELS_H
+#define UQ_CODEC_KERNELS_H
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace {
+
 constexpr int kTcProbBits = 12;
 constexpr uint32_t kTcM = 1u << kTcProbBits;
 constexpr uint32_t kTcL = 1u << 16;
@@ -685,3 +694,7 @@ tc_decode_kernel(const uint8_t* __restrict__ msgs, uint64_t msgs_bytes, const ui
         }
     }
 }
+
+}  // namespace
+
+#endif  // UQ_CODEC_KERNELS_H

@@ -1,5 +1,5 @@
 // uq_eden_kernels.h — EDEN with the randomized Hadamard transform.
-// Included by uq_dme.hip inside its anonymous namespace.
+// Included by uq_eden.hip.
 //
 // Reference (AS = NMSE_Results/Codes/All_Schemes.py):
 //   AS:100-115  Hadamard.hadamard: stages h = 2..D, a' = a + b, b' = a' - 2b (f32), then
@@ -23,13 +23,12 @@
 //                          lane), scale = f32(nrm*nrm) / dot; the receiver's first pass reads
 //                          the bins (MODE 2)
 
-// Orders one wave's LDS accesses across lanes: the compiler sees single-lane addresses only
-// (s[i] and s[i + 1] never alias for ONE lane) and could otherwise move a read past another
-// lane's write; the wave's LDS operations themselves execute in program order.
-__device__ __forceinline__ void wave_lds_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront", "local");
-    __builtin_amdgcn_wave_barrier();
-}
+#ifndef UQ_EDEN_KERNELS_H
+#define UQ_EDEN_KERNELS_H
+
+#include "uq_common.h"
+
+namespace {
 
 constexpr int kFwhtT = 256;            // threads per FWHT workgroup
 constexpr int kFwhtLowBits = 12;       // first pass: contiguous tiles of 4096
@@ -1678,3 +1677,7 @@ eden_normdot1_kernel(const float* __restrict__ v, int64_t n, int64_t D, float sq
         redo[vec] = ok ? 0 : 1;
     }
 }
+
+}  // namespace
+
+#endif  // UQ_EDEN_KERNELS_H

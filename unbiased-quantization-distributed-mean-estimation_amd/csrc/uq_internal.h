@@ -1,0 +1,73 @@
+// uq_internal.h — host functions and state that cross the library's translation units.
+//
+// Each scheme is one .hip (uq_dme.hip: core + unbiased, uq_biased.hip, uq_eden.hip,
+// uq_quicfl.hip, uq_codec.hip).  What they share on the host is declared here and defined in
+// exactly one of them, so every piece of state (the error string, the side streams, the
+// environment knobs) exists once in the library.  Nothing here is exported: the namespace has
+// hidden visibility.  Signatures use plain types only: the kernels' argument structs live in
+// anonymous namespaces (their names are part of the kernels' symbols), so they cannot cross.
+#ifndef UQ_INTERNAL_H
+#define UQ_INTERNAL_H
+
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+#include <string>
+
+#include "../../include/uq_dme.h"
+
+namespace uq_internal __attribute__((visibility("hidden"))) {
+
+constexpr int64_t kMaxGridY = 65535;       // clients per launch of the kernels with one grid row per client
+
+// ---- uq_dme.hip ----------------------------------------------------------------------
+// Records msg as the calling thread's uq_last_error() and returns code.
+int fail(int code, const std::string& msg);
+int hip_check(hipError_t e, const char* what);
+bool aligned16(const void* p);
+
+// AS:624 |x|.sum() of n rows in torch CPU order for T intra-op threads (K1a + K1b with AbsOp).
+// part: n * total_groups * 32 floats of the plan make_plan(d, T) gives; the caller has checked
+// that the plan exists.
+int launch_l1(const float* x, int64_t n, int64_t d, int32_t T, float* part, float* l1_out, hipStream_t st);
+
+// A second stream per device and thread (plus fork / join events) for work that can run
+// beside the caller's stream inside one call; joined back before the call returns.
+struct SideStream {
+    hipStream_t s;
+    hipEvent_t fork, join, mid;         // mid: KB7a's bandwidth-heavy first levels done
+    uint32_t* count;            // pinned host word (UQ_TIES_HOST_CHECK reads the tie list's length)
+    void* states;               // pinned host RezStates (the small-vector path's flags), kSmallCheckMaxN
+};
+constexpr int64_t kSmallCheckMaxN = 64;    // clients per host-checked small-vector biased call
+int side_stream(SideStream** out);
+
+// ---- uq_biased.hip -------------------------------------------------------------------
+// KB2's cap on level-1 groups per workgroup (env UQDME_HIST_GPW), read by launch_cascade for
+// the histogram op only.
+int hist_groups_per_wg();
+
+// ---- uq_eden.hip: the RHT and the norm as QUIC-FL's sender uses them -------------------
+// The EDEN workspace layout of (n, dim): D = dim padded to a power of two, the norms at
+// nrm_off, `total` bytes in all (QUIC-FL's own regions follow).
+struct RhtLayout {
+    size_t nrm_off, total;
+    int64_t D;
+};
+RhtLayout rht_layout(int64_t n, int64_t dim);
+// RHT (AS:123-141) and torch.norm (AS:329) of n rows in the workspace wsb; *rot = the rotated
+// vectors (one of the workspace's two vector buffers), the norms at rht_layout's nrm_off.
+int rht_norm_front(const float* x, int64_t n, int64_t dim, const int8_t* signs, const int32_t* sign_row, char* wsb,
+                   float** rot, hipStream_t st);
+// The receiver's inverse RHT (H, then * diag) of rot [n][D], in place but for the last pass,
+// which writes out [n][dim].
+int rht_inverse(float* rot, float* out, int64_t n, int64_t D, int64_t dim, const int8_t* signs,
+                const int32_t* sign_row, float sqrtD, hipStream_t st);
+
+}  // namespace uq_internal
+
+// (only the library's own translation units include this header)
+using namespace uq_internal;
+
+#endif  // UQ_INTERNAL_H

@@ -301,7 +301,7 @@ class MtPoly {
 
 }  // namespace
 
-// Internal entry points (declared in uq_dme.hip; uq_mt_jump_host is also in include/uq_dme.h).
+// Internal entry points (declared in uq_quicfl.hip; uq_mt_jump_host is also in include/uq_dme.h).
 extern "C" int uq_mtpoly_progression(int64_t b0, int64_t step, int32_t count, uint32_t* out) {
     MtPoly& m = MtPoly::get();
     if (!m.ok() || b0 < 0 || step < 0 || count < 0 || !out) return -1;

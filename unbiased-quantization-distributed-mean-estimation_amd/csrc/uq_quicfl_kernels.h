@@ -1,6 +1,5 @@
 // uq_quicfl_kernels.h — QUIC-FL sender and receiver streams.  Included by
-// uq_dme.hip inside its anonymous namespace, after uq_eden_kernels.h (the RHT and the norm are
-// EDEN's).
+// uq_quicfl.hip (the RHT and the norm are EDEN's: uq_eden.hip runs them, see uq_internal.h).
 //
 // Reference (AS = NMSE_Results/Codes/All_Schemes.py), QuicFLSender.compress AS:455-503:
 //   AS:457      prng_seed = xxh64(str(seed)) % 2^16; local generator seeded with it
@@ -31,6 +30,13 @@
 //   The global generator starts from ATen's state (left, next, 624 words): the first left - 1
 //   words are state[next ..], then twisted blocks; the state after the D draws is written back
 //   for the host to restore into torch's generator.
+
+#ifndef UQ_QUICFL_KERNELS_H
+#define UQ_QUICFL_KERNELS_H
+
+#include "uq_common.h"
+
+namespace {
 
 constexpr int kMtN = 624;              // MT19937 state words
 constexpr int kMtGroups = 10;          // 64-word groups per block (the last one 48 words)
@@ -1368,3 +1374,7 @@ quicfl_recv_fin_kernel(QflRecvArgs a, QflRunArgs ra) {
     if (a.compact && a.exact_count && tot != (int64_t)a.exact_count[j]) flags |= UQ_QFL_BAD_EXACT;
     if (lane == 0 && a.info) a.info[j] = flags;
 }
+
+}  // namespace
+
+#endif  // UQ_QUICFL_KERNELS_H
