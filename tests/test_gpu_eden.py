@@ -148,6 +148,21 @@ def test_rht_forward_two_and_three_passes_vs_oracle(uq, d):
     assert G.bits_equal(fwd, E.rht(x, 21))
 
 
+@pytest.mark.parametrize("p", [12, 13, 20, 21, 22])
+def test_rht_inverse_pass_counts_vs_oracle(uq, p):
+    """The stand-alone inverse RHT's own pass schedule (first pass 12 bits at most, then 8 at
+    most each) at the smallest D of each pass count: 2^12 (one pass), 2^13 (12 + 1), 2^20
+    (12 + 8), 2^21 (12 + 8 + 1), 2^22 (12 + 8 + 2).  Exact f32 butterflies in a fixed order:
+    bit-equal to the oracle."""
+    D = 1 << p
+    seeds = [21, 77]
+    v = np.random.default_rng(p).standard_normal((2, D)).astype(np.float32)
+    inv = uq.randomized_inverse_hadamard_transform(torch.as_tensor(v).cuda(), seeds).cpu().numpy()
+    assert inv.shape == (2, D)
+    for j, seed in enumerate(seeds):
+        assert G.bits_equal(inv[j], E.inverse_rht(v[j], seed)), (p, j)
+
+
 @pytest.mark.parametrize("d", [1, 2, 3, 5, 16, 100, 4095, 4096, 4097, 5000, 8192, 12289])
 def test_eden_dims_across_pass_shapes_vs_oracle(uq, d):
     """Dimensions around the pass shapes: a single generic pass (D < 4096), the low pass

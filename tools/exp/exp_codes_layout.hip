@@ -8,7 +8,7 @@
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -ffp-contract=off \
 //     -fhip-fp32-correctly-rounded-divide-sqrt -fno-gpu-flush-denormals-to-zero \
 //     -o tools/exp/libexp_codes_layout.so tools/exp/exp_codes_layout.hip
-#include "../../unbiased-quantization-distributed-mean-estimation_amd/csrc/uq_dme.hip"
+#include "../../unbiased-quantization-distributed-mean-estimation_amd/csrc/uq_unbiased_kernels.h"
 
 namespace {
 __global__ void __launch_bounds__(kQBlock, 4)

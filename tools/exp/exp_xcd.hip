@@ -20,7 +20,7 @@
 //     -> coalesced non-temporal stores of q and the int8 codes.
 // mode bit 0: skip the barrier waits (pure data flow: wrong numbers, timing bound).
 // Spins are bounded: a timeout sets err[0] and the workgroup continues (no hang).
-#include "../../unbiased-quantization-distributed-mean-estimation_amd/csrc/uq_dme.hip"
+#include "../../unbiased-quantization-distributed-mean-estimation_amd/csrc/uq_unbiased_kernels.h"
 
 namespace xcd {
 // W workgroups per CU (1 or 2): 1024/W threads, a team of 32*W workgroups per XCD, a slice

@@ -49,29 +49,28 @@ struct BiasedLayout {
 
 BiasedLayout biased_layout(int64_t n, int64_t d, const L1Plan& plan) {
     BiasedLayout w{};
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     w.tiles = (int32_t)((d + kSelTile - 1) / kSelTile);
     w.part_off = kCtrlBytes;
-    w.l1_off = up(w.part_off + (size_t)n * plan.total_groups * 32 * sizeof(float));
-    w.msum_off = up(w.l1_off + (size_t)n * sizeof(float));
-    w.st_off = up(w.msum_off + (size_t)n * sizeof(float));
-    w.hist_off = up(w.st_off + (size_t)n * sizeof(RezState));
+    w.l1_off = up256(w.part_off + (size_t)n * plan.total_groups * 32 * sizeof(float));
+    w.msum_off = up256(w.l1_off + (size_t)n * sizeof(float));
+    w.st_off = up256(w.msum_off + (size_t)n * sizeof(float));
+    w.hist_off = up256(w.st_off + (size_t)n * sizeof(RezState));
     w.cap = (uint32_t)std::min<int64_t>(std::max<int64_t>(d, 1), std::max<int64_t>(4096, d / 8));
     w.capf = w.cap / 2;
-    w.zn_off = up(w.hist_off + (size_t)n * kHistSlots * kRadixBins * sizeof(uint32_t));
+    w.zn_off = up256(w.hist_off + (size_t)n * kHistSlots * kRadixBins * sizeof(uint32_t));
     w.cn_off = w.zn_off + (size_t)n * 2 * sizeof(uint32_t);           // zn and cand_n adjacent
     w.fl_off = w.cn_off + (size_t)n * sizeof(uint32_t);               // the full clients' list (zeroed count)
-    w.cand_off = up(w.fl_off + (size_t)(n + 1) * sizeof(uint32_t));
-    w.tcnt_off = up(w.cand_off + (size_t)n * w.cap * sizeof(uint32_t));
-    w.bits_off = up(w.tcnt_off + (size_t)n * w.tiles * sizeof(uint32_t));
+    w.cand_off = up256(w.fl_off + (size_t)(n + 1) * sizeof(uint32_t));
+    w.tcnt_off = up256(w.cand_off + (size_t)n * w.cap * sizeof(uint32_t));
+    w.bits_off = up256(w.tcnt_off + (size_t)n * w.tiles * sizeof(uint32_t));
     w.slots = (int32_t)std::min<int64_t>(n, kTieSlots);
-    w.pairs_off = up(w.bits_off + (size_t)n * ((d + 31) / 32) * sizeof(uint32_t));
-    w.pos_off = up(w.pairs_off + (size_t)w.slots * 2 * ((d + 3) & ~(int64_t)3) * sizeof(uint32_t) + 16);
-    w.list_off = up(w.pos_off + (size_t)w.slots * 2 * d * sizeof(uint32_t));
-    w.tls_off = up(w.list_off + (size_t)(n + 1) * sizeof(uint32_t));    // KB7's client list
-    w.tcnt2_off = up(w.tls_off + (size_t)w.slots * sizeof(TieLevelState));
-    w.alist_off = up(w.tcnt2_off + (size_t)w.slots * kTieSegs * 2 * sizeof(uint32_t));
-    w.total = up(w.alist_off + (size_t)(kTieSlots + 1) * sizeof(uint32_t));    // KB7a's active slots
+    w.pairs_off = up256(w.bits_off + (size_t)n * ((d + 31) / 32) * sizeof(uint32_t));
+    w.pos_off = up256(w.pairs_off + (size_t)w.slots * 2 * ((d + 3) & ~(int64_t)3) * sizeof(uint32_t) + 16);
+    w.list_off = up256(w.pos_off + (size_t)w.slots * 2 * d * sizeof(uint32_t));
+    w.tls_off = up256(w.list_off + (size_t)(n + 1) * sizeof(uint32_t));    // KB7's client list
+    w.tcnt2_off = up256(w.tls_off + (size_t)w.slots * sizeof(TieLevelState));
+    w.alist_off = up256(w.tcnt2_off + (size_t)w.slots * kTieSegs * 2 * sizeof(uint32_t));
+    w.total = up256(w.alist_off + (size_t)(kTieSlots + 1) * sizeof(uint32_t));    // KB7a's active slots
     return w;
 }
 

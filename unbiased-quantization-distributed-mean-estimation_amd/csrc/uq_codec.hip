@@ -17,7 +17,7 @@ TcLayout tc_layout(int64_t n, int64_t d) {
     const int64_t csz = (int64_t)tc_lanes(d) * kTcSteps;
     TcLayout L;
     size_t o = 0;
-    auto take = [&](size_t b) { const size_t r = o; o += (b + 255) & ~(size_t)255; return r; };
+    auto take = [&](size_t b) { const size_t r = o; o += up256(b); return r; };
     L.hist = take((size_t)n * 256 * 4);
     L.tabs = take((size_t)n * sizeof(TcTable));
     L.cwords = take((size_t)(n * nch) * 4);

@@ -6,7 +6,7 @@
 // Everything is in an anonymous namespace on purpose: each translation unit gets its own copy
 // of what it uses (there is no device linking), nothing here has state, and the kernels'
 // symbols carry these types' names.  A kernel template is instantiated by the one translation
-// unit that launches it (the cascade with AbsOp: uq_dme.hip, with the Rez ops: uq_biased.hip).
+// unit that launches it (the cascade with AbsOp: uq_unbiased.hip, with the Rez ops: uq_biased.hip).
 #ifndef UQ_COMMON_H
 #define UQ_COMMON_H
 

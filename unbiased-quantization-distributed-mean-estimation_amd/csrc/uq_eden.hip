@@ -57,20 +57,19 @@ struct SegNormLayout {
     size_t segsum, g, e, kind, cnt, tseg, tab, thr, acc, total;      // offsets from the region start
 };
 SegNormLayout segnorm_layout(int64_t n, int64_t D) {
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const size_t nk = (size_t)n * 8 * (size_t)(D / kSegBlock);
     SegNormLayout L{};
     L.segsum = 0;
-    L.g = up(nk * sizeof(double));
-    L.e = up(L.g + nk * sizeof(float));
-    L.kind = up(L.e + nk * sizeof(float));
-    L.cnt = up(L.kind + nk * sizeof(int32_t));
-    L.tseg = up(L.cnt + (size_t)n * sizeof(int32_t));
+    L.g = up256(nk * sizeof(double));
+    L.e = up256(L.g + nk * sizeof(float));
+    L.kind = up256(L.e + nk * sizeof(float));
+    L.cnt = up256(L.kind + nk * sizeof(int32_t));
+    L.tseg = up256(L.cnt + (size_t)n * sizeof(int32_t));
     const size_t cap = (size_t)seg_tab_cap(D);
-    L.tab = up(L.tseg + (size_t)n * cap * sizeof(int32_t));
-    L.thr = up(L.tab + (size_t)n * cap * kSegTab * sizeof(float));   // KE4s: thresholds [n][4]
-    L.acc = up(L.thr + (size_t)n * 4 * sizeof(float));                 //       chain ends [n][64]
-    L.total = up(L.acc + (size_t)n * 64 * sizeof(float));
+    L.tab = up256(L.tseg + (size_t)n * cap * sizeof(int32_t));
+    L.thr = up256(L.tab + (size_t)n * cap * kSegTab * sizeof(float));   // KE4s: thresholds [n][4]
+    L.acc = up256(L.thr + (size_t)n * 4 * sizeof(float));                 //       chain ends [n][64]
+    L.total = up256(L.acc + (size_t)n * 64 * sizeof(float));
     return L;
 }
 
@@ -153,15 +152,14 @@ struct EdenLayout {
 
 EdenLayout eden_layout(int64_t n, int64_t dim) {
     EdenLayout w{};
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     w.D = dim <= 1 ? 1 : ((int64_t)1 << ilog2_pow2(dim));
     w.tiles = (int32_t)((w.D + kEdenTile - 1) / kEdenTile);
     w.vec_off = kCtrlBytes;
-    w.nrm_off = up(w.vec_off + (size_t)n * w.D * sizeof(float));
-    w.bins_off = up(w.nrm_off + (size_t)n * sizeof(float));
-    w.scale_off = up(w.bins_off + (size_t)n * w.D);
-    w.redo_off = up(w.scale_off + (size_t)n * sizeof(float));
-    w.seg_off = up(w.redo_off + (size_t)n * sizeof(int32_t));
+    w.nrm_off = up256(w.vec_off + (size_t)n * w.D * sizeof(float));
+    w.bins_off = up256(w.nrm_off + (size_t)n * sizeof(float));
+    w.scale_off = up256(w.bins_off + (size_t)n * w.D);
+    w.redo_off = up256(w.scale_off + (size_t)n * sizeof(float));
+    w.seg_off = up256(w.redo_off + (size_t)n * sizeof(int32_t));
     w.seg = segnorm_applies(n, w.D);
     w.total = w.seg_off + (w.seg ? segnorm_layout(n, w.D).total : 0);
     return w;
@@ -194,6 +192,26 @@ void fwht_dispatch(dim3 grid, const FwhtArgs& b, int lo, int k, hipStream_t st) 
         hipLaunchKernelGGL((fwht_pass_kernel<M, L, R>), grid, dim3(kFwhtT), 0, st, b, lo, k);
 }
 
+// The passes of one transform of 2^p elements, low bits first: the first pass takes up to
+// `first` bits (contiguous tiles), every later one up to kFwhtHighBits (2^k rows x kFwhtCols
+// columns).  lo0 > 0 resumes a transform whose passes below bit lo0 are done.
+struct FwhtPasses {
+    int p, lo, k;
+    FwhtPasses(int p_, int first, int lo0 = 0) : p(p_), lo(lo0), k(std::min(p_ - lo0, lo0 ? kFwhtHighBits : first)) {}
+    bool last() const { return lo + k >= p; }
+    int64_t tiles() const { return ((int64_t)1 << (p - k)) / (lo == 0 ? 1 : kFwhtCols); }
+    void next() { lo += k; k = std::min(p - lo, kFwhtHighBits); }
+};
+// First pass of the forward transform and the receivers' inverse: D = 2^22 (config C4) takes 14
+// bits, then 8 (one pass fewer than 12 + 8 + 2)
+int fwht_first_bits(int p) { return p == kFwhtLow16Bits + kFwhtHighBits ? kFwhtLow16Bits : kFwhtLowBits; }
+
+FwhtArgs fwht_args(const void* in, const int8_t* signs, const int32_t* sign_row, const uint32_t* sbits,
+                   const float* scale, int64_t D, int64_t dim, const EdenTables& tab) {
+    const float sqrtD = (float)std::sqrt((double)D);         // np.sqrt(d) -> f32 operand
+    return FwhtArgs{in, /*out (set per pass)*/ nullptr, signs, sign_row, sbits, scale, D, dim, sqrtD, tab};
+}
+
 // Runs the FWHT passes of one transform.  MODE of the first pass: 1 sender, 2 receiver.
 // Receiver: passes in place in `buf`, the last into `out`.  Sender: passes alternate
 // between `buf` and `out` (out == buf: in place; the forward RHT passes its output so
@@ -202,15 +220,10 @@ void fwht_dispatch(dim3 grid, const FwhtArgs& b, int lo, int k, hipStream_t st) 
 int launch_fwht(FwhtArgs a, int64_t n, bool receiver, float* buf, float* out, hipStream_t st,
                 float** result = nullptr, int lo0 = 0) {
     const int p = ilog2_pow2(a.D);
-    // D = 2^22 (config C4): a 14-bit first pass, then 8 (one pass fewer than 12 + 8 + 2)
-    int lo = lo0, k = std::min(p - lo0, lo0 ? kFwhtHighBits : (p == kFwhtLow16Bits + kFwhtHighBits ? kFwhtLow16Bits
-                                                                                                    : kFwhtLowBits));
-    bool first = lo0 == 0;
     float* cur = buf;                              // sender: the buffer the next pass writes
-    for (;;) {
-        const bool last = lo + k >= p;
-        const int cols = lo == 0 ? 1 : kFwhtCols;
-        const int64_t tiles = a.D / (((int64_t)1 << k) * cols);
+    for (FwhtPasses ps(p, fwht_first_bits(p), lo0);; ps.next()) {
+        const int lo = ps.lo, k = ps.k;
+        const bool first = lo == 0, last = ps.last();
         FwhtArgs b = a;
         if (receiver) {
             b.out = last ? out : buf;
@@ -221,7 +234,7 @@ int launch_fwht(FwhtArgs a, int64_t n, bool receiver, float* buf, float* out, hi
             if (result) *result = cur;
             cur = cur == buf ? out : buf;
         }
-        const dim3 grid((unsigned)tiles, (unsigned)n);
+        const dim3 grid((unsigned)ps.tiles(), (unsigned)n);
         if (first && !receiver) {
             if (last) fwht_dispatch<1, true, false>(grid, b, lo, k, st);
             else fwht_dispatch<1, false, false>(grid, b, lo, k, st);
@@ -238,11 +251,24 @@ int launch_fwht(FwhtArgs a, int64_t n, bool receiver, float* buf, float* out, hi
         int rc = hip_check(hipGetLastError(), "fwht_pass_kernel launch");
         if (rc) return rc;
         if (last) break;
-        first = false;
-        lo += k;
-        k = std::min(p - lo, kFwhtHighBits);
     }
     return UQ_OK;
+}
+
+// The inverse transform of plain vectors (H, then * diag on the last pass, no scale): the
+// first pass reads a.in, the passes run in place in `buf` and the last writes `out`.
+int launch_inverse_passes(const FwhtArgs& a, FwhtPasses ps, int64_t n, float* buf, float* out, hipStream_t st) {
+    for (;; ps.next()) {
+        const bool last = ps.last();
+        FwhtArgs b = a;
+        if (ps.lo > 0) b.in = buf;
+        b.out = last ? out : buf;
+        const dim3 grid((unsigned)ps.tiles(), (unsigned)n);
+        if (last) fwht_dispatch<0, true, true>(grid, b, ps.lo, ps.k, st);
+        else fwht_dispatch<0, false, false>(grid, b, ps.lo, ps.k, st);
+        const int rc = hip_check(hipGetLastError(), "fwht_pass_kernel launch");
+        if (rc || last) return rc;
+    }
 }
 
 int eden_check(int64_t n, int64_t dim, int32_t nbits, const int8_t* signs, EdenTables* tab) {
@@ -260,15 +286,7 @@ int eden_front(const float* x, int64_t n, int64_t dim, const EdenTables& tab, co
                const int32_t* sign_row, const EdenLayout& w, char* wsb, FwhtArgs& a, float** rot, hipStream_t st,
                const uint32_t* sbits = nullptr) {
     float* nrm = (float*)(wsb + w.nrm_off);
-    a = FwhtArgs{};
-    a.in = x;
-    a.signs = signs;
-    a.sign_row = sign_row;
-    a.sbits = sbits;
-    a.D = w.D;
-    a.dim = dim;
-    a.sqrtD = (float)std::sqrt((double)w.D);                 // np.sqrt(d) -> f32 operand
-    a.tab = tab;
+    a = fwht_args(x, signs, sign_row, sbits, nullptr, w.D, dim, tab);
     float* vec = (float*)(wsb + w.vec_off);
     int rc = launch_fwht(a, n, false, vec, vec, st, rot);
     if (rc) return rc;
@@ -292,30 +310,10 @@ int uq_internal::rht_norm_front(const float* x, int64_t n, int64_t dim, const in
 
 // AS:533-535: H, then * diag, [:dim]; D = 2^22 as 14 + 8 bits
 int uq_internal::rht_inverse(float* rot, float* out, int64_t n, int64_t D, int64_t dim, const int8_t* signs,
-                             const int32_t* sign_row, float sqrtD, hipStream_t st) {
+                             const int32_t* sign_row, hipStream_t st) {
+    const FwhtArgs a = fwht_args(rot, signs, sign_row, nullptr, nullptr, D, dim, EdenTables{});
     const int p = ilog2_pow2(D);
-    int lo = 0, k = p == kFwhtLow16Bits + kFwhtHighBits ? kFwhtLow16Bits : std::min(p, kFwhtLowBits);
-    for (;;) {
-        const bool last = lo + k >= p;
-        const int cols = lo == 0 ? 1 : kFwhtCols;
-        const int64_t tiles = D / (((int64_t)1 << k) * cols);
-        FwhtArgs b{};
-        b.in = rot;
-        b.out = last ? out : rot;
-        b.signs = signs;
-        b.sign_row = sign_row;
-        b.scale = nullptr;
-        b.D = D;
-        b.dim = dim;
-        b.sqrtD = sqrtD;
-        const dim3 grid((unsigned)tiles, (unsigned)n);
-        if (last) fwht_dispatch<0, true, true>(grid, b, lo, k, st);
-        else fwht_dispatch<0, false, false>(grid, b, lo, k, st);
-        const int rc = hip_check(hipGetLastError(), "fwht_pass_kernel launch");
-        if (rc || last) return rc;
-        lo += k;
-        k = std::min(p - lo, kFwhtHighBits);
-    }
+    return launch_inverse_passes(a, FwhtPasses(p, fwht_first_bits(p)), n, rot, out, st);
 }
 
 extern "C" {
@@ -341,14 +339,7 @@ int uq_rht_f32(const float* x, float* out, int64_t n, int64_t dim, int32_t inver
     // the transform uses the vector region only (no norm: the segmented-norm tables past
     // seg_off are not needed here)
     if (!ws || ws_bytes < w.seg_off) return fail(UQ_E_WORKSPACE, "workspace too small");
-    FwhtArgs a{};
-    a.in = x;
-    a.signs = signs;
-    a.sign_row = sign_row;
-    a.scale = nullptr;
-    a.D = w.D;
-    a.dim = inverse ? w.D : dim;
-    a.sqrtD = (float)std::sqrt((double)w.D);
+    const FwhtArgs a = fwht_args(x, signs, sign_row, nullptr, nullptr, w.D, inverse ? w.D : dim, EdenTables{});
     hipStream_t st = (hipStream_t)stream;
     float* buf = (float*)((char*)ws + w.vec_off);
     if (!inverse) {                                           // AS:123-141: pad, * diag, H
@@ -358,28 +349,10 @@ int uq_rht_f32(const float* x, float* out, int64_t n, int64_t dim, int32_t inver
         return hip_check(hipMemcpyAsync(out, buf, (size_t)n * w.D * sizeof(float), hipMemcpyDeviceToDevice, st),
                          "copy rht");
     }
-    // AS:146-153: H, then * diag (the receiver's last pass with no scale)
-    const int p = ilog2_pow2(w.D);
-    int lo = 0, k = std::min(p, kFwhtLowBits);
-    bool first = true;
-    for (;;) {
-        const bool last = lo + k >= p;
-        const int cols = lo == 0 ? 1 : kFwhtCols;
-        const int64_t tiles = w.D / (((int64_t)1 << k) * cols);
-        FwhtArgs b = a;
-        b.in = first ? (const void*)x : (const void*)buf;
-        b.out = last ? out : buf;
-        const dim3 grid((unsigned)tiles, (unsigned)n);
-        if (last) fwht_dispatch<0, true, true>(grid, b, lo, k, st);
-        else fwht_dispatch<0, false, false>(grid, b, lo, k, st);
-        int rc = hip_check(hipGetLastError(), "fwht_pass_kernel launch");
-        if (rc) return rc;
-        if (last) break;
-        first = false;
-        lo += k;
-        k = std::min(p - lo, kFwhtHighBits);
-    }
-    return UQ_OK;
+    // AS:146-153: H, then * diag (the receiver's last pass with no scale).  This entry's first
+    // pass takes 12 bits at most whatever D, so D = 2^22 runs 12 + 8 + 2 here, not the 14 + 8
+    // of fwht_first_bits: another width would launch other kernels.
+    return launch_inverse_passes(a, FwhtPasses(ilog2_pow2(w.D), kFwhtLowBits), n, buf, out, st);
 }
 
 int uq_eden_workspace_bytes(int64_t n, int64_t dim, size_t* bytes_out) {
@@ -444,14 +417,7 @@ int uq_eden_compress_f32_sb(const float* x, int64_t n, int64_t dim, int32_t nbit
     if (!w.seg && tab.nb == 1 && w.D % kNormChunk == 0) {
         // 1 bit, many clients: the norm, the bins and the dot in one read (KE2+4), then KE4 for
         // the clients it flags (a norm that is not positive and finite, an underflowing quotient)
-        FwhtArgs a{};
-        a.in = x;
-        a.signs = signs;
-        a.sign_row = sign_row;
-        a.sbits = sign_bits;
-        a.D = w.D;
-        a.dim = dim;
-        a.sqrtD = (float)std::sqrt((double)w.D);
+        const FwhtArgs a = fwht_args(x, signs, sign_row, sign_bits, nullptr, w.D, dim, EdenTables{});
         float* vec = (float*)(wsb + w.vec_off);
         float* rot = nullptr;
         rc = launch_fwht(a, n, false, vec, vec, st, &rot);                          // AS:123-141
@@ -488,16 +454,7 @@ int uq_eden_decompress_f32_sb(const uint8_t* bins, const float* scale, int64_t n
     if (!bins || !scale || !out) return fail(UQ_E_INVALID, "null pointer");
     const EdenLayout w = eden_layout(n, dim);
     if (!ws || ws_bytes < w.total) return fail(UQ_E_WORKSPACE, "workspace too small");
-    FwhtArgs a{};
-    a.in = bins;
-    a.signs = signs;
-    a.sign_row = sign_row;
-    a.sbits = sign_bits;
-    a.scale = scale;
-    a.D = w.D;
-    a.dim = dim;
-    a.sqrtD = (float)std::sqrt((double)w.D);
-    a.tab = tab;
+    const FwhtArgs a = fwht_args(bins, signs, sign_row, sign_bits, scale, w.D, dim, tab);
     return launch_fwht(a, n, true, (float*)((char*)ws + w.vec_off), out, (hipStream_t)stream);   // AS:378-413
 }
 

@@ -1,11 +1,12 @@
 // uq_internal.h — host functions and state that cross the library's translation units.
 //
-// Each scheme is one .hip (uq_dme.hip: core + unbiased, uq_biased.hip, uq_eden.hip,
-// uq_quicfl.hip, uq_codec.hip).  What they share on the host is declared here and defined in
-// exactly one of them, so every piece of state (the error string, the side streams, the
-// environment knobs) exists once in the library.  Nothing here is exported: the namespace has
-// hidden visibility.  Signatures use plain types only: the kernels' argument structs live in
-// anonymous namespaces (their names are part of the kernels' symbols), so they cannot cross.
+// Each scheme is one .hip (uq_unbiased.hip, uq_biased.hip, uq_eden.hip, uq_quicfl.hip,
+// uq_codec.hip) beside the host core, uq_core.hip.  What they share on the host is declared
+// here and defined in exactly one of them, so every piece of state (the error string, the side
+// streams, the environment knobs) exists once in the library.  Nothing here is exported: the
+// namespace has hidden visibility.  Signatures use plain types only: the kernels' argument
+// structs live in anonymous namespaces (their names are part of the kernels' symbols), so they
+// cannot cross.
 #ifndef UQ_INTERNAL_H
 #define UQ_INTERNAL_H
 
@@ -21,16 +22,14 @@ namespace uq_internal __attribute__((visibility("hidden"))) {
 
 constexpr int64_t kMaxGridY = 65535;       // clients per launch of the kernels with one grid row per client
 
-// ---- uq_dme.hip ----------------------------------------------------------------------
+// Workspace regions start on 256-byte boundaries: v rounded up to the next one.
+constexpr size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// ---- uq_core.hip ---------------------------------------------------------------------
 // Records msg as the calling thread's uq_last_error() and returns code.
 int fail(int code, const std::string& msg);
 int hip_check(hipError_t e, const char* what);
 bool aligned16(const void* p);
-
-// AS:624 |x|.sum() of n rows in torch CPU order for T intra-op threads (K1a + K1b with AbsOp).
-// part: n * total_groups * 32 floats of the plan make_plan(d, T) gives; the caller has checked
-// that the plan exists.
-int launch_l1(const float* x, int64_t n, int64_t d, int32_t T, float* part, float* l1_out, hipStream_t st);
 
 // A second stream per device and thread (plus fork / join events) for work that can run
 // beside the caller's stream inside one call; joined back before the call returns.
@@ -42,6 +41,12 @@ struct SideStream {
 };
 constexpr int64_t kSmallCheckMaxN = 64;    // clients per host-checked small-vector biased call
 int side_stream(SideStream** out);
+
+// ---- uq_unbiased.hip -----------------------------------------------------------------
+// AS:624 |x|.sum() of n rows in torch CPU order for T intra-op threads (K1a + K1b with AbsOp).
+// part: n * total_groups * 32 floats of the plan make_plan(d, T) gives; the caller has checked
+// that the plan exists.
+int launch_l1(const float* x, int64_t n, int64_t d, int32_t T, float* part, float* l1_out, hipStream_t st);
 
 // ---- uq_biased.hip -------------------------------------------------------------------
 // KB2's cap on level-1 groups per workgroup (env UQDME_HIST_GPW), read by launch_cascade for
@@ -63,7 +68,7 @@ int rht_norm_front(const float* x, int64_t n, int64_t dim, const int8_t* signs, 
 // The receiver's inverse RHT (H, then * diag) of rot [n][D], in place but for the last pass,
 // which writes out [n][dim].
 int rht_inverse(float* rot, float* out, int64_t n, int64_t D, int64_t dim, const int8_t* signs,
-                const int32_t* sign_row, float sqrtD, hipStream_t st);
+                const int32_t* sign_row, hipStream_t st);
 
 }  // namespace uq_internal
 

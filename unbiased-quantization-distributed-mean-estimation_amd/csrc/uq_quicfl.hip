@@ -1,12 +1,14 @@
 // uq_quicfl.hip — QUIC-FL: the jump plans, the launchers of uq_quicfl_kernels.h and the C API
 // of the sender (uq_quicfl_compress_f32, uq_quicfl_quantize_f32) and the receiver
-// (uq_quicfl_receive_*).  The RHT and the norm run in uq_eden.hip.
+// (uq_quicfl_receive_*), and uq_xxh64 (the sender's prng seed).  The RHT and the norm run in
+// uq_eden.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <atomic>
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <map>
 #include <mutex>
 #include <tuple>
@@ -251,10 +253,10 @@ int uq_quicfl_prepare_f32(const int32_t* X, int64_t n, int64_t D, const float* r
 // Workspace: the EDEN layout (rotated vectors, norms, segmented-norm region) + h [n][D] u8 +
 // the jump path's blocks [n][R][3][624] u32 and run records [n][R][2] i32.
 static size_t quicfl_h_off(int64_t n, int64_t dim) {
-    return (rht_layout(n, dim).total + 255) & ~(size_t)255;
+    return up256(rht_layout(n, dim).total);
 }
 static size_t quicfl_jump_off(int64_t n, int64_t dim) {
-    return (quicfl_h_off(n, dim) + (size_t)n * (size_t)rht_layout(n, dim).D + 255) & ~(size_t)255;
+    return up256(quicfl_h_off(n, dim) + (size_t)n * (size_t)rht_layout(n, dim).D);
 }
 // jump region: streams [n][2][kMjX], parts [n][R][3][kMjParts][624], run records [n][R][2]
 // (without the jump path: the local blocks after KQ1a, [n][624])
@@ -564,7 +566,48 @@ int uq_quicfl_quantize_f32(const float* x, int64_t n, int64_t dim, const int8_t*
     q.pre = rot;                       // in place: a coordinate's rot is loaded a round before its value is stored
     rc = launch_quicfl_send(q, 2, jl, st);              // (2: the fused instances)                 AS:455-503, 526-532
     if (rc) return rc;
-    return rht_inverse(rot, out, n, w.D, dim, signs, sign_row, q.sqrtD, st);                  // AS:533-535
+    return rht_inverse(rot, out, n, w.D, dim, signs, sign_row, st);                           // AS:533-535
+}
+
+// xxHash64 (the public XXH64 algorithm), for AS:457's prng seed
+static inline uint64_t xxh_rotl(uint64_t x, int r) { return (x << r) | (x >> (64 - r)); }
+static inline uint64_t xxh_read64(const uint8_t* p) { uint64_t v; std::memcpy(&v, p, 8); return v; }
+static inline uint32_t xxh_read32(const uint8_t* p) { uint32_t v; std::memcpy(&v, p, 4); return v; }
+
+uint64_t uq_xxh64(const void* data, size_t len, uint64_t seed) {
+    const uint64_t P1 = 0x9E3779B185EBCA87ull, P2 = 0xC2B2AE3D27D4EB4Full, P3 = 0x165667B19E3779F9ull,
+                   P4 = 0x85EBCA77C2B2AE63ull, P5 = 0x27D4EB2F165667C5ull;
+    auto round = [&](uint64_t acc, uint64_t lane) { return xxh_rotl(acc + lane * P2, 31) * P1; };
+    const uint8_t* p = (const uint8_t*)data;
+    const uint8_t* end = p + len;
+    uint64_t h;
+    if (len >= 32) {
+        uint64_t v1 = seed + P1 + P2, v2 = seed + P2, v3 = seed, v4 = seed - P1;
+        while (p + 32 <= end) {
+            v1 = round(v1, xxh_read64(p));
+            v2 = round(v2, xxh_read64(p + 8));
+            v3 = round(v3, xxh_read64(p + 16));
+            v4 = round(v4, xxh_read64(p + 24));
+            p += 32;
+        }
+        h = xxh_rotl(v1, 1) + xxh_rotl(v2, 7) + xxh_rotl(v3, 12) + xxh_rotl(v4, 18);
+        for (uint64_t v : {v1, v2, v3, v4}) h = (h ^ round(0, v)) * P1 + P4;
+    } else {
+        h = seed + P5;
+    }
+    h += (uint64_t)len;
+    for (; p + 8 <= end; p += 8) h = xxh_rotl(h ^ round(0, xxh_read64(p)), 27) * P1 + P4;
+    if (p + 4 <= end) {
+        h = xxh_rotl(h ^ ((uint64_t)xxh_read32(p) * P1), 23) * P2 + P3;
+        p += 4;
+    }
+    for (; p < end; ++p) h = xxh_rotl(h ^ ((uint64_t)*p * P5), 11) * P1;
+    h ^= h >> 33;
+    h *= P2;
+    h ^= h >> 29;
+    h *= P3;
+    h ^= h >> 32;
+    return h;
 }
 
 }  // extern "C"
