@@ -53,6 +53,35 @@ int uq_test_force_replay_failure(int on);
  * sender's few-message calls to the team kernel KQ1t instead of the jump path (KQ0j + KQ1j), so
  * the forms can be compared on the same message.  Returns the previous flags. */
 int uq_test_set_quicfl_hooks(int flags);
+/* Test hooks of the unbiased quantizer's dispatch (every uq_type_unbiased_* entry point runs one
+ * dispatcher, and the dispatcher launches what its plan names).
+ * A plan is UQ_PLAN_FIELDS int64 values, of which min(cap, UQ_PLAN_FIELDS) are written:
+ *   [0] form (UQ_FORM_*)   [1] V: float4 lanes for x and q   [2] Q: q written   [3] C: codes written
+ *   [4] CV: 16-byte code rows   [5] l1 supplied by the caller   [6] chunks of at most 65535 clients
+ *   of the last chunk: [7] clients   [8] prefixed (the approximate-prefix launch)   [9] tiles per
+ *   segment   [10] segments per client
+ *   [11] tiles per client   byte offsets in the workspace of [12] the u64 [n][tiles] array that
+ *   holds the fold's exact tile starts P_t after a segments / phased call, [13] map0, [14] map1,
+ *   [15] the irregular tiles' records ([min(n, [19])][[18]] of [17] bytes, the event count in the
+ *   first 32-bit word), [16] their u32 counters (the last chunk's, one per client)
+ *   [17] sizeof(TileRec)   [18] records per client   [19] clients with records   [20] events per
+ *   record   [21] events the fold prefetches
+ * uq_test_unbiased_plan: host only, the plan of a call of that shape (alignment and presence of
+ * the pointers as flags; slots = resident stream workgroups, 0 asks the current device when the
+ * plan needs it); UQ_E_INVALID where the call would be refused for its shape.
+ * uq_test_last_unbiased_plan: the plan of this thread's last unbiased call (form 0 when it
+ * launched nothing). */
+#define UQ_PLAN_FIELDS 22
+#define UQ_FORM_NONE 0
+#define UQ_FORM_SMALL 1
+#define UQ_FORM_STREAM 2
+#define UQ_FORM_STREAM_NIBBLES 3
+#define UQ_FORM_SEGMENTS 4
+#define UQ_FORM_PHASED 5
+int uq_test_unbiased_plan(int64_t n, int64_t d, int64_t ldq, int64_t ldc, int32_t x_aligned, int32_t out_aligned,
+                          int32_t codes_aligned, int32_t has_out, int32_t has_codes, int32_t nib, int32_t l1_given,
+                          int32_t slots, int64_t* plan_out, int32_t cap);
+int uq_test_last_unbiased_plan(int64_t* plan_out, int32_t cap);
 /* Host-only, for tests and tools: the MT19937 state (ATen's 624-word array, block-aligned) that
  * `blocks` twists ahead of state624, computed the way the QUIC-FL sender's jump path does it
  * (t^(624 (blocks - 1)) mod phi, phi from Berlekamp-Massey; the correlation with the stream's

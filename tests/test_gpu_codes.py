@@ -1,11 +1,12 @@
-"""GPU: type codes from the quantize kernels (stream and small-batch paths), decode, and the
-mean from codes -- all bit-exact against the oracle / the float path."""
+"""GPU: type codes from the quantize kernels (small, stream, segments and phased forms, each
+asserted through the dispatch hook), decode, and the mean from codes -- all bit-exact against the oracle / the float path."""
 import numpy as np
 import pytest
 import torch
 
 from oracle import uq_oracle as O
 from tests import golden_data as G
+from tests import plan_hook as H
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -17,7 +18,11 @@ def uq(gpu_ready):
     return uqdme
 
 
-@pytest.mark.parametrize("n,d", [(5, 4099), (3, 100003), (300, 4096), (260, 1001), (2, 1 << 20)])
+FORMS = {(5, 4099): H.PHASED, (3, 100003): H.PHASED, (300, 4096): H.SMALL, (260, 1001): H.PHASED,
+         (2, 1 << 20): H.PHASED, (256, 32784): H.STREAM}
+
+
+@pytest.mark.parametrize("n,d", [(5, 4099), (3, 100003), (300, 4096), (260, 1001), (2, 1 << 20), (256, 32784)])
 def test_codes_match_oracle_and_decode(uq, n, d):
     rng = np.random.default_rng(n * 7 + d)
     x = rng.laplace(1, 2, (n, d)).astype(f32)
@@ -25,6 +30,8 @@ def test_codes_match_oracle_and_decode(uq, n, d):
     for R in (1, 2):
         m = O.rate_to_m(R, d)
         tc, q = uq.quantize_encode(torch.from_numpy(x).cuda(), m=m, X=X, torch_threads=1, return_q=True)
+        p = H.last_plan(uq.load_library())
+        assert p["form"] == FORMS[(n, d)] and p["Q"] and p["C"], p
         q_only = uq.quantize_dequantize(torch.from_numpy(x).cuda(), m=m, X=X, torch_threads=1)
         assert torch.equal(q.view(torch.int32), q_only.view(torch.int32))
         tc.check()
@@ -39,6 +46,8 @@ def test_codes_match_oracle_and_decode(uq, n, d):
         assert G.bits_equal(dec.cpu().numpy(), q.cpu().numpy())
         # encode-only path (no q written) gives the same codes
         tc2 = uq.quantize_encode(torch.from_numpy(x).cuda(), m=m, X=X, torch_threads=1)
+        p = H.last_plan(uq.load_library())
+        assert p["form"] == FORMS[(n, d)] and not p["Q"] and p["C"], p
         assert torch.equal(tc2.codes, tc.codes)
         est = uq.codes_mean(tc, n)
         assert G.bits_equal(est.cpu().numpy(), uq.client_mean(q, n).cpu().numpy())

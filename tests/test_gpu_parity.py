@@ -9,6 +9,8 @@ import torch
 from oracle import uq_oracle as O
 from oracle import uq_oracle_c as C
 from tests import golden_data as G
+from tests import plan_hook as H
+from tests.guard_batches import division_guard_batch as _division_guard_batch
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -273,39 +275,13 @@ def test_l1_many_chunks_over_finalize_waves(uq):
     assert G.bits_equal(qb, eb), G.n_mismatch(qb, eb)
 
 
-def _division_guard_batch(n, d, rng):
-    """Rows that drive every branch of the kernels' x / den (div_plan / div4): ordinary
-    rows (fast path), rows with tiny, subnormal, huge and non-finite elements (per-element
-    IEEE fallback), zero-heavy rows (zeros stay on the fast path), a row with L1 >= 2^40
-    (whole client on the IEEE division), an all-zero row (den = 1e-12) and rows whose
-    quotients all fall under the guard threshold."""
-    x = rng.standard_normal((n, d)).astype(f32)
-    for j in range(n):
-        kind = j % 8
-        idx = rng.integers(0, d, size=max(1, d // 64))
-        if kind == 1:
-            x[j, idx] *= np.float32(1e-40)                        # subnormal elements
-        elif kind == 2:
-            x[j, idx] = (rng.standard_normal(idx.size) * 1e-25).astype(f32)   # tiny normals
-        elif kind == 3:
-            x[j] *= np.float32(1e10)                              # L1 >= 2^40: IEEE path per client
-        elif kind == 4:
-            x[j, rng.random(d) < 0.9] = 0.0                       # sparse: zeros on the fast path
-        elif kind == 5:
-            x[j] *= np.float32(1e-30)                             # every quotient under the threshold
-        elif kind == 6:
-            x[j, idx[:3]] = [np.inf, -np.inf, np.nan][: min(3, idx.size)]
-        elif kind == 7:
-            x[j, idx] *= np.float32(1e30)                         # huge elements, q still finite
-    x[n // 2] = 0.0                                               # den = 1e-12 exactly
-    return x
-
-
-@pytest.mark.parametrize("n,d", [(264, 4100), (3, 70001)])
+@pytest.mark.parametrize("n,d", [(264, 4100), (3, 70001), (264, 32772)])
 def test_division_guards_stream_and_small_batch(uq, n, d):
     """x / den is computed with a per-client reciprocal and two fma corrections; every
-    guard branch must give the IEEE quotient's bits (n >= 256: stream kernel, one
-    workgroup per client; n = 3: the small-batch kernels)."""
+    guard branch must give the IEEE quotient's bits: (264, 4100) in the small kernel (aligned
+    rows of d < 32768), (3, 70001) in the phased kernels on scalar lanes, (264, 32772) in the
+    stream kernel (n >= 256 and d >= 32768), each asserted through the dispatch hook."""
+    form = {(264, 4100): H.SMALL, (3, 70001): H.PHASED, (264, 32772): H.STREAM}[(n, d)]
     rng = np.random.default_rng(4242 + n)
     x = _division_guard_batch(n, d, rng)
     assert float(np.abs(x[3 % n]).astype(np.float64).sum()) >= 2.0 ** 40 or n < 4
@@ -313,6 +289,7 @@ def test_division_guards_stream_and_small_batch(uq, n, d):
     for R in (1, 4):
         m = O.rate_to_m(R, d)
         got = uq.quantize_dequantize(dev(x), m=m, X=X, torch_threads=1).cpu().numpy()
+        assert H.last_plan(uq.load_library())["form"] == form
         ref, _ = C.quantize_batch(x, m, X, 1)
         assert G.n_mismatch(got, ref) == 0, (n, d, R, [G.n_mismatch(got[j], ref[j]) for j in range(n)][:16])
 
@@ -348,20 +325,23 @@ def test_k2_forms_agree_stream_segmented_per_tile(uq, n, d):
 
 @pytest.mark.parametrize("R", [0.5, 6.5, 10])
 def test_stream_form_all_rates_and_ragged_rows(uq, R):
-    """n >= 256 (stream kernel) at low and high rates: k >= 256 takes the arithmetic output
-    path (the running-max bound on the table), heavy tails make large k, and d is not a
-    multiple of the tile."""
+    """256 clients at low and high rates: k >= 256 takes the arithmetic output path (the
+    running-max bound on the table), heavy tails make large k, and d is not a multiple of the
+    tile.  d = 12308 runs the small kernel (aligned rows of d < 32768), d = 32788 the stream
+    kernel, each asserted through the dispatch hook."""
     rng = np.random.default_rng(int(R * 10))
-    n, d = 256, 3 * 4096 + 20
-    x = rng.laplace(1, 2, (n, d)).astype(f32)
-    x[::7] *= np.float32(50.0)
-    X = rng.random(n).astype(f32)
-    m = O.rate_to_m(R, d)
-    got = uq.quantize_dequantize(dev(x), m=m, X=X, torch_threads=1).cpu().numpy()
-    ref, _ = C.quantize_batch(x, m, X, 1)
-    assert G.n_mismatch(got, ref) == 0
-    tc, q = uq.quantize_encode(dev(x), m=m, X=X, torch_threads=1, return_q=True)
-    assert G.bits_equal(q.cpu().numpy(), ref)
+    for (n, d), form in (((256, 3 * 4096 + 20), H.SMALL), ((256, 8 * 4096 + 20), H.STREAM)):
+        x = rng.laplace(1, 2, (n, d)).astype(f32)
+        x[::7] *= np.float32(50.0)
+        X = rng.random(n).astype(f32)
+        m = O.rate_to_m(R, d)
+        got = uq.quantize_dequantize(dev(x), m=m, X=X, torch_threads=1).cpu().numpy()
+        assert H.last_plan(uq.load_library())["form"] == form
+        ref, _ = C.quantize_batch(x, m, X, 1)
+        assert G.n_mismatch(got, ref) == 0
+        tc, q = uq.quantize_encode(dev(x), m=m, X=X, torch_threads=1, return_q=True)
+        assert H.last_plan(uq.load_library())["form"] == form
+        assert G.bits_equal(q.cpu().numpy(), ref)
 
 
 def test_l1_thread_counts_match_torch_fixture(uq):

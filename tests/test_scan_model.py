@@ -32,6 +32,41 @@ def test_tree_scan_differs_on_the_gpu_test_inputs():
     assert X is not None and i > 0
 
 
+@pytest.mark.parametrize("seed", [6, 8, 9, 23, 65])
+def test_tree_scan_tile_prefixes_differ_at_most_tiles(seed):
+    """Comparing the fold's exact tile starts P_t (tests/test_gpu_exact_scan.py) has teeth: on
+    each of that test's seeds the tree scheme's tile-end prefixes differ from the sequential
+    fp64 cumsum at nearly every one of the 256 tiles (249-254 when this was written), while one
+    crafted X exposes a single element."""
+    d = 1 << 20
+    fr = fractions(S.tiny_mix(seed, d), O.rate_to_m(1, d))
+    ends = np.arange(1, d // S.TILE + 1) * S.TILE - 1
+    seq = np.cumsum(fr.astype(f64))[ends]
+    tre = S.tree_prefix(fr)[ends]
+    differ = int((seq.view(np.uint64) != tre.view(np.uint64)).sum())
+    assert differ >= 200, differ
+
+
+def test_fold_census_of_the_gpu_test_inputs():
+    """The census model of the fold's per-tile paths (scan_models.fold_census) on the inputs of
+    tests/test_gpu_exact_scan.py: the tiny mixes have a handful of irregular tiles, some recorded,
+    far from the record budget and the fold's prefetch; the hover vector goes past both, and the
+    exact scheme still reproduces its sequential cumsum."""
+    d = 1 << 20
+    c = S.fold_census(fractions(S.tiny_mix(6, d), O.rate_to_m(1, d)))
+    assert 5 <= int(c["irregular"].sum()) <= 16 and 0 < c["n_recorded"] <= S.REC_PER_CLIENT
+    assert c["rec_events"] <= S.FOLD_EVENTS and not c["other_binade"].any() and c["irregular"][0]
+    x, l1, m = S.hover_vector(1 << 22)
+    _, _, fr = O.fractional_parts(x, m, l1)
+    c = S.fold_census(fr)
+    assert c["n_recorded"] == 33 > S.REC_PER_CLIENT and c["rec_events"] > S.FOLD_EVENTS
+    assert int(c["events"].max()) <= S.REC_EVENTS and not c["other_binade"].any()
+    x, l1, m = S.hover_vector(1 << 17)
+    _, _, fr = O.fractional_parts(x, m, l1)
+    assert S.fold_census(fr)["n_recorded"] >= 11
+    assert np.array_equal(np.cumsum(fr.astype(f64)).view(np.uint64), S.exact_prefix(fr).view(np.uint64))
+
+
 def _compose_scan(d0, d1):
     """The small-batch fold's wave scan (exact_fold_kernel): maps P -> P + d[P & 1] in
     integer units of G, Hillis-Steele over 64 lanes with (F then g).d[p] =

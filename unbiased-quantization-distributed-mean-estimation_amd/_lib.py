@@ -24,6 +24,9 @@ SIGNATURES = {
     "uq_build_id": (ctypes.c_char_p, []),
     "uq_test_force_replay_failure": (ctypes.c_int, [ctypes.c_int]),
     "uq_test_set_quicfl_hooks": (ctypes.c_int, [ctypes.c_int]),
+    "uq_test_unbiased_plan": (ctypes.c_int, [_i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p,
+                                             _i32]),
+    "uq_test_last_unbiased_plan": (ctypes.c_int, [_p, _i32]),
     "uq_mt_jump_host": (ctypes.c_int, [_p, _i64, _p]),
     "uq_legacy_draw_f32": (ctypes.c_int, [_p, _p, _p, _p, _i32, _f64, _f64, _i64, _i64, _p, _p, _i32]),
     "uq_legacy_test_params": (ctypes.c_int, [_i64, _i64, _p, _p]),

@@ -179,6 +179,122 @@ bool select_vqc(bool v, bool q, bool c, bool cv, F&& f) {
 
 int bad_selector() { return fail(UQ_E_INVALID, "internal: bad kernel selector"); }
 
+// ---- dispatch plan -------------------------------------------------------------------
+// Every decision of unbiased_codes_impl, made on the host from the call's shape alone: which
+// K2 form runs, which template instance of it, and how the clients are chunked.  The dispatcher
+// launches what the plan names and nothing else decides, so the test hooks
+// (uq_test_unbiased_plan, uq_test_last_unbiased_plan) report what a call really runs.
+struct PlanIn {
+    int64_t n, d, ldo, ldc;
+    bool x16, out16, codes16;          // 16-byte alignment of the base pointers
+    bool has_out, has_codes, nib, l1_given;
+    int slots;                         // resident stream workgroups; 0: ask the device when needed
+};
+struct ChunkPlan {                     // one chunk of at most kMaxGridY clients (segments / phased)
+    int64_t nj;
+    bool seg;
+    int32_t prefixed, R, nseg;
+};
+struct UnbiasedPlan {
+    int32_t form;                      // UQ_FORM_*
+    bool V, Q, C, CV, l1_given;
+    int64_t chunks;
+    ChunkPlan last;                    // the last chunk (chunked forms; otherwise nj = n, R = tiles)
+    int32_t tiles;
+    size_t agg_off, map0_off, map1_off, rec_off, cnt_off;
+};
+
+int chunk_plan(const PlanIn& in, const UnbiasedPlan& p, int64_t j0, ChunkPlan* c) {
+    c->nj = std::min<int64_t>(kMaxGridY, in.n - j0);
+    const int64_t total_tiles = c->nj * (int64_t)p.tiles;
+    c->seg = p.V && in.d <= ((int64_t)1 << 29) && total_tiles >= kSegMinTiles;
+    c->R = 1;
+    c->nseg = 1;
+    if (c->seg) {
+        // segmented stream: runs of R tiles per workgroup, ~4 resident workgroups per CU
+        int slots = in.slots;
+        if (slots <= 0) {
+            const int rc = stream_slots(&slots);
+            if (rc) return rc;
+        }
+        // at most `slots` workgroups in all, so that they run as one wave: ceil(total / slots)
+        // tiles each made nj * ceil(tiles / R) > slots workgroups for most nj (101 x 2^22:
+        // 1111 of 1024 slots, the last 87 workgroups a second round of R tiles)
+        const int64_t segs = std::max<int64_t>(1, slots / c->nj);
+        c->R = (int32_t)((p.tiles + segs - 1) / segs);
+        c->nseg = (p.tiles + c->R - 1) / c->R;
+    }
+    c->prefixed = c->nj >= 4 ? 1 : 0;
+    return UQ_OK;
+}
+
+// in: a call with n > 0 and d > 0 whose pitches were checked; w: its workspace layout.
+int plan_unbiased(const PlanIn& in, const WsLayout& w, UnbiasedPlan* p) {
+    *p = UnbiasedPlan{};
+    if (!in.has_out && !in.has_codes) return fail(UQ_E_INVALID, "nothing to write: out and codes are both NULL");
+    const int64_t n = in.n, d = in.d;
+    p->tiles = w.tiles;
+    p->agg_off = w.agg_off;
+    p->map0_off = w.incl_off;
+    p->map1_off = w.map1_off;
+    p->rec_off = w.rec_off;
+    p->cnt_off = w.cnt_off;
+    p->Q = in.has_out;
+    p->C = in.has_codes;
+    p->l1_given = in.l1_given;
+    // rows are 16-byte aligned when d % 4 == 0, or when there is only one row
+    p->V = in.x16 && (!in.has_out || in.out16) && ((d % 4 == 0 && in.ldo % 4 == 0) || n == 1);
+    p->CV = !in.has_codes || (in.codes16 && d % 16 == 0 && (in.ldc % 16 == 0 || n == 1));
+    p->chunks = 1;
+    p->last = ChunkPlan{n, false, 0, w.tiles, 1};
+    if (!in.nib && d <= kSmallL1Max && p->V && n <= 0x7FFFFFFF) {
+        p->form = UQ_FORM_SMALL;
+        return UQ_OK;
+    }
+    const bool stream_form = n >= kStreamMinClients && p->V && d <= ((int64_t)1 << 29);
+    if (in.nib) {
+        if (!stream_form || !in.has_out || !in.has_codes)
+            return fail(UQ_E_INVALID, "internal: 4-bit codes outside the stream form");
+        p->form = UQ_FORM_STREAM_NIBBLES;
+        p->CV = true;
+        return UQ_OK;
+    }
+    if (stream_form) {
+        p->form = UQ_FORM_STREAM;
+        return UQ_OK;
+    }
+    // Small batches: clients go in chunks of at most kMaxGridY.
+    p->chunks = (n + kMaxGridY - 1) / kMaxGridY;
+    const int rc = chunk_plan(in, *p, (p->chunks - 1) * kMaxGridY, &p->last);
+    if (rc) return rc;
+    p->form = p->last.seg ? UQ_FORM_SEGMENTS : UQ_FORM_PHASED;
+    return UQ_OK;
+}
+
+bool bad_pitches(bool has_out, int64_t ldo, bool has_codes, int64_t ldc, int64_t d, bool nib) {
+    return (has_out && ldo < d) || (has_codes && ldc < (nib ? d / 2 : d));
+}
+
+// 4-bit codes exist in the stream form only, whole mean threads per row
+bool bad_nibble_shape(int64_t n, int64_t d) {
+    return n < kStreamMinClients || d % kNibAlign != 0 || d > ((int64_t)1 << 29);
+}
+int nibble_shape_error() {
+    return fail(UQ_E_INVALID, "4-bit codes need n >= 256 and d a multiple of 4096 (<= 2^29)");
+}
+
+thread_local UnbiasedPlan t_last_plan{};     // uq_test_last_unbiased_plan
+
+int export_plan(const UnbiasedPlan& p, int64_t* out, int32_t cap) {
+    if (!out || cap < 0) return fail(UQ_E_INVALID, "null plan output");
+    const int64_t f[UQ_PLAN_FIELDS] = {
+        p.form, p.V, p.Q, p.C, p.CV, p.l1_given, p.chunks, p.last.nj, p.last.prefixed, p.last.R, p.last.nseg,
+        p.tiles, (int64_t)p.agg_off, (int64_t)p.map0_off, (int64_t)p.map1_off, (int64_t)p.rec_off, (int64_t)p.cnt_off,
+        (int64_t)sizeof(TileRec), kRecPerClient, kRecClients, kRecEvents, kFoldEvents};
+    for (int i = 0; i < std::min<int32_t>(cap, UQ_PLAN_FIELDS); ++i) out[i] = f[i];
+    return UQ_OK;
+}
+
 // AS:609-641 for a batch.  X: per-client draws (device), or nullptr with n == 1 and the one
 // draw passed by value in Xval (the per-call drop-in: no host-to-device copy of X).
 // Row j of q at out + j*ldo, of the codes at codes + j*ldc (ldo, ldc >= d: row pitches let the
@@ -192,19 +308,23 @@ int unbiased_codes_impl(const float* x, float* out, int64_t ldo, int8_t* codes, 
     WsLayout w;
     int rc = check_common(x, n, d, T, ws, ws_bytes, &plan, &w);
     if (rc) return rc;
+    t_last_plan = UnbiasedPlan{};
     if (m < 0) return fail(UQ_E_INVALID, "m must be >= 0");
-    if ((out && ldo < d) || (codes && ldc < (nib ? d / 2 : d))) return fail(UQ_E_INVALID, "row pitches must be >= d");
+    if (bad_pitches(out, ldo, codes, ldc, d, nib)) return fail(UQ_E_INVALID, "row pitches must be >= d");
     if (n == 0 || d == 0) return UQ_OK;
     if (!X && n != 1) return fail(UQ_E_INVALID, "null X");
-    if (!out && !codes) return fail(UQ_E_INVALID, "nothing to write: out and codes are both NULL");
+    const PlanIn in{n, d, ldo, ldc, aligned16(x), aligned16(out), aligned16(codes), out != nullptr, codes != nullptr,
+                    nib, l1 != nullptr, 0};
+    UnbiasedPlan P;
+    rc = plan_unbiased(in, w, &P);
+    if (rc) return rc;
     if (codes && !overflow) return fail(UQ_E_INVALID, "codes need a kmax[n] array");
+    t_last_plan = P;
     hipStream_t st = (hipStream_t)stream;
     const float* l1use = l1;
     const float fm = (float)m;   // torch casts the Python int to f32 for `m * p` and `/ m`
-    // rows are 16-byte aligned when d % 4 == 0, or when there is only one row
-    const bool vec4 = aligned16(x) && (!out || aligned16(out)) && ((d % 4 == 0 && ldo % 4 == 0) || n == 1);
-    const bool cvec = !codes || (aligned16(codes) && d % 16 == 0 && (ldc % 16 == 0 || n == 1));
-    if (!nib && d <= kSmallL1Max && vec4 && n <= 0x7FFFFFFF) {
+    const bool vec4 = P.V, cvec = P.CV;
+    if (P.form == UQ_FORM_SMALL) {
         // shorter than GRAIN: L1 (one torch cascade for any thread count) and the exact scan
         // in one workgroup per client, one launch
         if (!select_qc(out, codes, cvec, [&](auto Q, auto C, auto CV) {
@@ -224,18 +344,17 @@ int unbiased_codes_impl(const float* x, float* out, int64_t ldo, int8_t* codes, 
         rc = hip_check(hipMemcpyAsync(l1_out, l1use, n * sizeof(float), hipMemcpyDeviceToDevice, st), "copy l1");
         if (rc) return rc;
     }
-    const bool stream_form = n >= kStreamMinClients && vec4 && d <= ((int64_t)1 << 29);
+    const bool stream_form = P.form == UQ_FORM_STREAM || P.form == UQ_FORM_STREAM_NIBBLES;
     if (codes && !stream_form) {          // the stream form stores each client's kmax itself
         rc = hip_check(hipMemsetAsync(overflow, 0, n * sizeof(int32_t), st), "memset kmax");
         if (rc) return rc;
     }
-    if (nib) {
-        if (!stream_form || !out || !codes) return fail(UQ_E_INVALID, "internal: 4-bit codes outside the stream form");
+    if (P.form == UQ_FORM_STREAM_NIBBLES) {
         hipLaunchKernelGGL((quantize_stream_kernel<true, true, true, true>), dim3((unsigned)n), dim3(kQBlock), 0, st, x,
                            out, codes, overflow, d, w.tiles, fm, X, Xval, l1use, w.tiles, 1, nullptr, ldo, ldc);
         return hip_check(hipGetLastError(), "quantize_stream_kernel (4-bit codes) launch");
     }
-    if (stream_form) {
+    if (P.form == UQ_FORM_STREAM) {
         // enough clients to fill the GPU: one workgroup per client vector
         if (!select_qc(out, codes, cvec, [&](auto Q, auto C, auto CV) {
                 hipLaunchKernelGGL((quantize_stream_kernel<Q(), C(), CV()>), dim3((unsigned)n), dim3(kQBlock), 0, st, x,
@@ -247,7 +366,10 @@ int unbiased_codes_impl(const float* x, float* out, int64_t ldo, int8_t* codes, 
     // Small batches: approximate sums -> approximate prefixes -> exact maps -> exact fold
     // -> outputs (see "small-batch forms").  Clients go in chunks of at most kMaxGridY.
     for (int64_t j0 = 0; j0 < n; j0 += kMaxGridY) {
-        const int64_t nj = std::min<int64_t>(kMaxGridY, n - j0);
+        ChunkPlan ck;
+        rc = chunk_plan(in, P, j0, &ck);
+        if (rc) return rc;
+        const int64_t nj = ck.nj;
         const float* xj = x + j0 * d;
         float* outj = out ? out + j0 * ldo : nullptr;
         int8_t* codesj = codes ? codes + j0 * ldc : nullptr;
@@ -259,21 +381,10 @@ int unbiased_codes_impl(const float* x, float* out, int64_t ldo, int8_t* codes, 
         uint64_t* map1 = w.tile_row(ws, w.map1_off, j0);
         TileRec* recs = w.at<TileRec>(ws, w.rec_off);
         uint32_t* reccnt = w.at<uint32_t>(ws, w.cnt_off);     // zeroed by the tile-sum kernels
-        const int64_t total_tiles = nj * (int64_t)w.tiles;
-        const bool seg = vec4 && d <= ((int64_t)1 << 29) && total_tiles >= kSegMinTiles;
+        const bool seg = ck.seg;
         const dim3 tgrid((unsigned)w.tiles, (unsigned)nj);
-        int32_t R = 1, nseg = 1;
+        const int32_t R = ck.R, nseg = ck.nseg;
         if (seg) {
-            // segmented stream: runs of R tiles per workgroup, ~4 resident workgroups per CU
-            int slots = 0;
-            rc = stream_slots(&slots);
-            if (rc) return rc;
-            // at most `slots` workgroups in all, so that they run as one wave: ceil(total / slots)
-            // tiles each made nj * ceil(tiles / R) > slots workgroups for most nj (101 x 2^22:
-            // 1111 of 1024 slots, the last 87 workgroups a second round of R tiles)
-            const int64_t segs = std::max<int64_t>(1, slots / nj);
-            R = (int32_t)((w.tiles + segs - 1) / segs);
-            nseg = (w.tiles + R - 1) / R;
             hipLaunchKernelGGL(agg_stream_kernel, dim3((unsigned)(nj * nseg)), dim3(kQBlock), 0, st, xj, d, w.tiles, fm,
                                l1j, R, nseg, agg, reccnt);
         } else if (vec4) {
@@ -283,7 +394,7 @@ int unbiased_codes_impl(const float* x, float* out, int64_t ldo, int8_t* codes, 
         }
         rc = hip_check(hipGetLastError(), "tile sums launch");
         if (rc) return rc;
-        const int32_t prefixed = nj >= 4 ? 1 : 0;
+        const int32_t prefixed = ck.prefixed;
         if (prefixed) {
             hipLaunchKernelGGL(tile_prefix_kernel, dim3((unsigned)nj), dim3(kQBlock), 0, st, agg, w.tiles);
             rc = hip_check(hipGetLastError(), "tile_prefix_kernel launch");
@@ -341,8 +452,7 @@ int uq_type_unbiased_nibbles_ld_f32(const float* x, float* out, int64_t ldq, uin
     if (n < 0 || d < 0) return fail(UQ_E_INVALID, "n and d must be >= 0");
     if (n == 0 || d == 0) return UQ_OK;
     if (!x || !out || !nib || !kmax || !X) return fail(UQ_E_INVALID, "null pointer (x, out, codes, kmax and X are required)");
-    if (n < kStreamMinClients || d % kNibAlign != 0 || d > ((int64_t)1 << 29))
-        return fail(UQ_E_INVALID, "4-bit codes need n >= 256 and d a multiple of 4096 (<= 2^29)");
+    if (bad_nibble_shape(n, d)) return nibble_shape_error();
     if (ldq < d || ldq % 4 != 0 || ldn < d / 2 || ldn % 16 != 0 || !aligned16(x) || !aligned16(out) || !aligned16(nib))
         return fail(UQ_E_INVALID, "4-bit codes need 16-byte aligned rows: ldq >= d, ldq % 4 == 0, ldn >= d/2, ldn % 16 == 0");
     return unbiased_codes_impl(x, out, ldq, (int8_t*)nib, ldn, kmax, n, d, m, X, 0.0f, l1, l1_out, T, ws, ws_bytes,
@@ -464,5 +574,29 @@ int uq_type_unbiased_mean_f32(const float* x, float* out, int64_t n, int64_t d, 
     if (rc) return rc;
     return uq_client_mean_f32(out, n, d, d, n_div, accumulate, est, stream);
 }
+
+int uq_test_unbiased_plan(int64_t n, int64_t d, int64_t ldq, int64_t ldc, int32_t x_aligned, int32_t out_aligned,
+                          int32_t codes_aligned, int32_t has_out, int32_t has_codes, int32_t nib, int32_t l1_given,
+                          int32_t slots, int64_t* plan_out, int32_t cap) {
+    L1Plan l1plan;
+    if (n < 0 || d < 0) return fail(UQ_E_INVALID, "n and d must be >= 0");
+    if (n > (int64_t)1 << 31 || d > (int64_t)1 << 40) return fail(UQ_E_INVALID, "n or d too large");
+    if (slots < 0) return fail(UQ_E_INVALID, "slots must be >= 0");
+    if (!make_plan(d, 1, &l1plan)) return fail(UQ_E_INVALID, "cannot build L1 plan");
+    const WsLayout w = layout(n, d, l1plan);       // (the offsets reported do not depend on torch_threads)
+    if ((int64_t)w.tiles * n > 0xFFFFFFFFll) return fail(UQ_E_INVALID, "batch too large for one call");
+    if (bad_pitches(has_out, ldq, has_codes, ldc, d, nib)) return fail(UQ_E_INVALID, "row pitches must be >= d");
+    UnbiasedPlan P{};
+    if (n > 0 && d > 0) {
+        if (nib && bad_nibble_shape(n, d)) return nibble_shape_error();
+        const PlanIn in{n, d, ldq, ldc, x_aligned != 0, out_aligned != 0, codes_aligned != 0, has_out != 0,
+                        has_codes != 0, nib != 0, l1_given != 0, slots};
+        const int rc = plan_unbiased(in, w, &P);
+        if (rc) return rc;
+    }
+    return export_plan(P, plan_out, cap);
+}
+
+int uq_test_last_unbiased_plan(int64_t* plan_out, int32_t cap) { return export_plan(t_last_plan, plan_out, cap); }
 
 }  // extern "C"
