@@ -53,6 +53,31 @@ int uq_test_force_replay_failure(int on);
  * sender's few-message calls to the team kernel KQ1t instead of the jump path (KQ0j + KQ1j), so
  * the forms can be compared on the same message.  Returns the previous flags. */
 int uq_test_set_quicfl_hooks(int flags);
+/* Test hooks of the QUIC-FL dispatch (each sender or receiver call computes one plan and launches
+ * what it names; DESIGN.md 4.4 has the table).  A plan is UQ_QFL_PLAN_FIELDS int64 values, of
+ * which min(cap, UQ_QFL_PLAN_FIELDS) are written:
+ *   [0] form (UQ_QFL_FORM_*)   jump form: [1] R runs per message of [2] L rounds, [3] two run
+ *   waves per SIMD (more than 1024 run waves); else 0   [4] force_timeout (hook bit 0)
+ *   [5] the sender's work on the side stream (UQ_QFL_SIDE_*: nothing, KQ1a, KQ0s + KQ0j + KQ1ar)
+ * uq_test_quicfl_plan: host only, launches nothing: the plan of side (UQ_QFL_SENDER /
+ * UQ_QFL_RECEIVER) for n messages of D (padded) coordinates under `hooks`, with (has_ws != 0) or
+ * without a workspace of the size the side's *_workspace_bytes gives (the sender's entry points
+ * refuse a call without one).  Form 0 for n == 0 or D == 0.
+ * uq_test_last_quicfl_plan: the plan of this thread's last call of that side (form 0 when it
+ * launched nothing). */
+#define UQ_QFL_PLAN_FIELDS 6
+#define UQ_QFL_SENDER 0
+#define UQ_QFL_RECEIVER 1
+#define UQ_QFL_FORM_NONE 0
+#define UQ_QFL_FORM_ONE_WAVE 1
+#define UQ_QFL_FORM_TEAM 2
+#define UQ_QFL_FORM_JUMP 3
+#define UQ_QFL_SIDE_NONE 0
+#define UQ_QFL_SIDE_PASS_A 1
+#define UQ_QFL_SIDE_JUMP 2
+int uq_test_quicfl_plan(int32_t side, int64_t n, int64_t D, int32_t hooks, int32_t has_ws, int64_t* plan_out,
+                        int32_t cap);
+int uq_test_last_quicfl_plan(int32_t side, int64_t* plan_out, int32_t cap);
 /* Test hooks of the unbiased quantizer's dispatch (every uq_type_unbiased_* entry point runs one
  * dispatcher, and the dispatcher launches what its plan names).
  * A plan is UQ_PLAN_FIELDS int64 values, of which min(cap, UQ_PLAN_FIELDS) are written:

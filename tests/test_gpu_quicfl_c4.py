@@ -16,6 +16,7 @@ import torch
 pytestmark = pytest.mark.gpu
 HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 sys.path.insert(0, HERE)
+from tests import quicfl_plan_hook as H  # noqa: E402
 from quicfl_tables import DATA, SR_BITS, data_txt, sender_tables  # noqa: E402
 
 
@@ -69,7 +70,12 @@ def test_sender_receiver_2pow22_vs_reference(fx, hooks):
             assert int(msg["scale"].cpu().numpy().view(np.uint32)) == c["scale_bits"], k
             w = state_words()
             assert (w[0], w[1]) == (c["left1"], c["next1"]) and np.array_equal(w[2:], z[f"st1_{k}"]), k
+            # one message of 2^22: both jump forms; hook 2 the one-wave, hook 4 the team kernels
+            form = {0: H.JUMP, 2: H.ONE_WAVE, 4: H.TEAM}[hooks]
+            p = H.last_plan(load(), H.SENDER)
+            assert p["form"] == form and p["side"] == {0: H.SIDE_JUMP, 2: H.SIDE_PASS_A, 4: H.SIDE_NONE}[hooks], p
             out = rx.decompress(msg).cpu().numpy()
+            assert H.last_plan(load(), H.RECEIVER)["form"] == form
             assert np.array_equal(out[z[f"opos{k}"]].view(np.uint32), z[f"rxs{k}"].view(np.uint32)), k
             assert sha(out) == c["rx_sha"], k
     finally:

@@ -13,6 +13,7 @@ import torch
 
 from oracle import uq_eden as E
 from oracle import uq_quicfl as Q
+from tests import quicfl_plan_hook as H
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -69,6 +70,17 @@ def set_global(gseed, pre):
 def state_words():
     import uqdme_amd.quicfl as q
     return q.generator_words(torch.default_generator)[1]
+
+
+def last_form(side, hooks=0):
+    """The form this thread's last call of that side took; its other fields are checked against
+    the form (the sender's side-stream work, the runs only in the jump form, the timeout hook)."""
+    from uqdme_amd._lib import load
+    p = H.last_plan(load(), side)
+    want = {H.ONE_WAVE: H.SIDE_PASS_A, H.TEAM: H.SIDE_NONE, H.JUMP: H.SIDE_JUMP}[p["form"]] if side == H.SENDER else H.SIDE_NONE
+    assert p["side"] == want and p["force_timeout"] == bool(hooks & 1), p
+    assert (p["R"] >= 1 and p["L"] >= 1) if p["form"] == H.JUMP else (p["R"], p["L"], p["two_wave"]) == (0, 0, False), p
+    return p["form"]
 
 
 def test_sender_matches_reference(fx):
@@ -196,11 +208,13 @@ def test_batch_states_and_many_messages(fx):
         states[j] = q.generator_words(g)[1]
     msg, new = q.quicfl_compress(torch.from_numpy(x), nbits, seeds, [123] * n, sender=snd, px_states=states,
                                  _state_out=True)
+    assert last_form(H.SENDER) == H.ONE_WAVE
     # the first 20 messages again as a few-message call (the jump path: every run's generator
     # blocks by jump-ahead, KQ0j): the same bits and end states as the batch's one-wave-per-
     # message kernel
     few, fnew = q.quicfl_compress(torch.from_numpy(x[:20]), nbits, seeds[:20], [123] * 20, sender=snd,
                                   px_states=states[:20], _state_out=True)
+    assert last_form(H.SENDER) == H.JUMP
     assert torch.equal(few.X, msg.X[:20]) and torch.equal(few.exact_mask, msg.exact_mask[:20])
     assert torch.equal(few.scale, msg.scale[:20]) and torch.equal(few.exact_count, msg.exact_count[:20])
     for j in range(20):
@@ -213,6 +227,7 @@ def test_batch_states_and_many_messages(fx):
     try:
         team, tnew = q.quicfl_compress(torch.from_numpy(x[:20]), nbits, seeds[:20], [123] * 20, sender=snd,
                                        px_states=states[:20], _state_out=True)
+        assert last_form(H.SENDER, 4) == H.TEAM
     finally:
         load().uq_test_set_quicfl_hooks(prev)
     assert torch.equal(team.X, few.X) and torch.equal(team.exact_count, few.exact_count) and np.array_equal(tnew, fnew)
@@ -232,8 +247,9 @@ def test_batch_states_and_many_messages(fx):
 def test_fused_quantize_equals_compress_then_decompress(fx, hooks):
     """quicfl_quantize (uq_quicfl_quantize_f32: the receiver fused into the sender's stage 2 with
     the sender's own h, AS:526-532) gives the bits of compress -> decompress and the same end
-    generator states, through the jump path (hooks 0: KQ0j + KQ1j), the one-wave kernels
-    (hooks 2) and the team kernels (hooks 4)."""
+    generator states, through the jump path (hooks 0: KQ0j + KQ1j; the receiver's jump path or
+    team kernel), the one-wave kernels (hooks 2) and the team kernels (hooks 4).  (4, 700) is
+    D = 1024, below both team kernels' shortest message: the one-wave kernels under every hook."""
     import uqdme
     import uqdme_amd.quicfl as q
     from uqdme_amd._lib import load
@@ -242,7 +258,11 @@ def test_fused_quantize_equals_compress_then_decompress(fx, hooks):
     rng = np.random.default_rng(40 + hooks)
     prev = load().uq_test_set_quicfl_hooks(hooks)
     try:
-        for nbits, n, dim in ((1, 3, 20000), (2, 2, 4099), (4, 1, 1 << 16), (3, 4, 700)):
+        # sender and receiver forms at hooks 0; hooks 4: the team kernels but for D = 1024
+        for nbits, n, dim, sform, rform in ((1, 3, 20000, H.JUMP, H.JUMP), (2, 2, 4099, H.JUMP, H.TEAM),
+                                            (4, 1, 1 << 16, H.JUMP, H.JUMP), (3, 4, 700, H.ONE_WAVE, H.ONE_WAVE)):
+            if hooks:
+                sform = rform = H.ONE_WAVE if hooks == 2 or dim == 700 else H.TEAM
             x = (rng.standard_normal((n, dim)) * 2).astype(np.float32)
             x[0, 5] = 500.0                                          # exact coordinates too
             seeds = [int(s) for s in rng.integers(0, 100, n)]
@@ -256,9 +276,12 @@ def test_fused_quantize_equals_compress_then_decompress(fx, hooks):
             states = np.stack(states)
             msg, new = q.quicfl_compress(torch.from_numpy(x), nbits, seeds, rots, sender=snd, px_states=states,
                                          x_dtype=torch.int64, _state_out=True)
+            assert last_form(H.SENDER, hooks) == sform, (n, dim)
             ref = uqdme.quicfl_decompress_messages(msg, rz[f"recv{nbits}"]).cpu().numpy()
+            assert last_form(H.RECEIVER, hooks) == rform, (n, dim)
             out, fnew, sc = uqdme.quicfl_quantize(torch.from_numpy(x), nbits, seeds, rots, sender=snd,
                                                   recv_table=rz[f"recv{nbits}"], px_states=states)
+            assert last_form(H.SENDER, hooks) == sform, (n, dim)
             assert out.cpu().numpy().view(np.uint32).tolist() == ref.view(np.uint32).tolist(), (nbits, n, dim)
             assert np.array_equal(fnew, new) and torch.equal(sc, msg.scale)
     finally:
@@ -331,12 +354,14 @@ def test_jump_path_equals_one_wave_across_shapes(fx, n, dim):
     cuts the streams differently) against the one-wave kernel (test hook 2) on the same
     messages: X, mask, exact values, scales, generator end states; px states off the block
     edge and fresh px seeds.  (300, 2^16): 3 runs per message past the team kernel's 256;
-    (342, 2^18): 5 runs, 1710 run waves, the two-waves-per-SIMD runs kernel."""
+    (342, 2^18): 5 runs, 1710 run waves, the two-waves-per-SIMD runs kernel.  (1, 4096) and
+    (128, 2^14) are where the cost model leaves the team kernel."""
     import uqdme_amd.quicfl as q
     from uqdme_amd._lib import load
     meta, z, rmeta, rz = fx
     snd = senders(meta)["pub"]
     rng = np.random.default_rng(n * 1000 + dim % 997)
+    form = H.TEAM if (n, dim) in ((1, 4096), (128, 1 << 14)) else H.JUMP
     x = (rng.standard_normal((n, dim)) * rng.uniform(0.5, 4, (n, 1))).astype(np.float32)
     x[0, 1] = 1e4                                                 # an exact coordinate at least
     seeds = [int(s) for s in rng.integers(0, 100, n)]
@@ -357,6 +382,9 @@ def test_jump_path_equals_one_wave_across_shapes(fx, n, dim):
                 try:
                     out[hooks] = q.quicfl_compress(torch.from_numpy(x), nbits, seeds, rots, sender=snd,
                                                    _state_out=True, **kw)
+                    assert last_form(H.SENDER, hooks) == (H.ONE_WAVE if hooks else form)
+                    if not hooks and form == H.JUMP:
+                        assert H.last_plan(load(), H.SENDER)["two_wave"] == (n == 342)
                 finally:
                     load().uq_test_set_quicfl_hooks(prev)
             (a, sa), (b, sb) = out[0], out[2]
@@ -392,6 +420,10 @@ def test_two_runs_per_message_at_900_messages(fx):
         try:
             m = q.quicfl_compress(x, nbits, seeds, rots, sender=snd, px_seeds=pxs)
             out[hooks] = (m, q.quicfl_decompress_messages(m, rt))
+            for side in (H.SENDER, H.RECEIVER):
+                assert last_form(side, hooks) == (H.ONE_WAVE if hooks else H.JUMP)
+                p = H.last_plan(load(), side)
+                assert hooks or (p["R"], p["L"], p["two_wave"]) == (2, 211, True), p
         finally:
             load().uq_test_set_quicfl_hooks(prev)
     (a, da), (b, db) = out[0], out[2]
@@ -401,4 +433,120 @@ def test_two_runs_per_message_at_900_messages(fx):
     assert torch.equal(da.view(torch.int32), db.view(torch.int32))
     # the receiver fused into the two-wave runs (QUICFL_quantize's path) gives the same batch
     fo, _, fsc = q.quicfl_quantize(x, nbits, seeds, rots, sender=snd, recv_table=rt, px_seeds=pxs)
+    assert last_form(H.SENDER) == H.JUMP and H.last_plan(load(), H.SENDER)["two_wave"]
     assert torch.equal(fo.view(torch.int32), da.view(torch.int32)) and torch.equal(fsc, a.scale)
+
+
+# (n, D) -> (sender form, receiver form given a workspace) without hooks, and nbits by dim
+MATRIX_FORMS = {(1, 1024): (H.ONE_WAVE, H.ONE_WAVE), (3, 1024): (H.ONE_WAVE, H.ONE_WAVE),
+                (1, 4096): (H.TEAM, H.ONE_WAVE), (3, 4096): (H.TEAM, H.ONE_WAVE),
+                (1, 8192): (H.JUMP, H.TEAM), (3, 8192): (H.JUMP, H.TEAM),
+                (1, 32768): (H.JUMP, H.JUMP), (3, 32768): (H.JUMP, H.JUMP), (342, 1 << 17): (H.JUMP, H.JUMP)}
+MATRIX_BITS = {700: 3, 4096: 4, 5000: 1, 20000: 2, 1 << 17: 1}
+_matrix_cache = {}
+
+
+def _matrix_inputs(dim, rz, rmeta):
+    """One batch per dim, shared by its cases (n = 1 is its first row): 3 rows on the host with
+    the oracle's message, end state and decompressed row of each; 342 rows on the GPU for 2^17."""
+    import uqdme_amd.quicfl as q
+    if dim in _matrix_cache:
+        return _matrix_cache[dim]
+    nbits, rows = MATRIX_BITS[dim], 342 if dim == 1 << 17 else 3
+    rng = np.random.default_rng(dim)
+    seeds = [int(s) for s in rng.integers(0, 100, rows)]
+    rots = [int(s) for s in rng.integers(0, 200, rows)]
+    g = torch.Generator()
+    states = np.empty((rows, 626), np.uint32)
+    for j in range(rows):
+        g.manual_seed(int(j * 104729 + dim))
+        torch.rand(1 + int(rng.integers(0, 1300)), generator=g)           # off the block edge
+        states[j] = q.generator_words(g)[1]
+    oracle = None
+    if rows == 3:
+        x = (rng.standard_normal((rows, dim)) * rng.uniform(0.5, 3, (rows, 1))).astype(np.float32)
+        x[:, 5] = 500.0                                                   # an exact coordinate in every row
+        tX, tp = sender_tables(nbits)
+        oracle = []
+        for j in range(rows):
+            exp, gst = _oracle_row(x[j], nbits, seeds[j], rots[j], tX, tp, DATA[nbits],
+                                   (int(states[j, 0]), int(states[j, 1]), states[j, 2:]))
+            rec = E.quicfl_decompress(exp["X"], rz[f"recv{nbits}"], rmeta["tables"][str(nbits)]["h_len"], exp["prng_seed"],
+                                      exp["exact_indeces"], exp["exact_values"], exp["scale"], rots[j], dim)
+            oracle.append((exp, gst, rec))
+        x = torch.from_numpy(x)
+    else:
+        x = torch.randn(rows, dim, generator=torch.Generator(device="cuda").manual_seed(17), device="cuda") * 2.0
+        x[:, 5] = 500.0
+    if oracle is not None:                                                # (the 180 MB batch has one case)
+        _matrix_cache[dim] = (x, seeds, rots, states, oracle)
+    return x, seeds, rots, states, oracle
+
+
+def _same_messages(a, sa, b, sb):
+    assert a.X.dtype == b.X.dtype and torch.equal(a.X, b.X) and torch.equal(a.exact_mask, b.exact_mask)
+    assert torch.equal(a.exact_count, b.exact_count) and torch.equal(a.scale, b.scale)
+    keep = torch.arange(a.X.shape[1], device=a.X.device)[None, :] < a.exact_count.to(a.X.device)[:, None]
+    assert torch.equal(a.exact_vals[keep].view(torch.int32), b.exact_vals[keep].view(torch.int32))
+    assert np.array_equal(sa, sb)
+
+
+@pytest.mark.parametrize("dim,n", [(700, 1), (700, 3), (4096, 1), (4096, 3), (5000, 1), (5000, 3), (20000, 1), (20000, 3),
+                                   (1 << 17, 342)])
+def test_every_form_equals_one_wave_and_oracle(fx, dim, n):
+    """One case per form and side at the smallest shapes that reach it -- D = 1024 the one-wave
+    kernels, 4096 the sender's team kernel, 8192 the sender's jump form and the receiver's team
+    kernel, 32768 both jump forms, 342 x 2^17 the two-wave runs of both -- for uint8 and int64 X
+    and the fused quantize.  The form is asserted through the plan hook; X, mask, exact values,
+    counts, scales, end states and the decompressed batch equal the one-wave kernels' (hook 2)
+    bit for bit, and up to 20000 coordinates the oracle's."""
+    import uqdme_amd.quicfl as q
+    from uqdme_amd._lib import load
+    meta, z, rmeta, rz = fx
+    snd = senders(meta)["pub"]
+    nbits = MATRIX_BITS[dim]
+    x, seeds, rots, states, oracle = _matrix_inputs(dim, rz, rmeta)
+    x, seeds, rots, states = x[:n], seeds[:n], rots[:n], states[:n]
+    rt = rz[f"recv{nbits}"]
+    D = 1 << (dim - 1).bit_length()
+    sform, rform = MATRIX_FORMS[(n, D)]
+    res = {}
+    for hooks in (0, 2):
+        prev = load().uq_test_set_quicfl_hooks(hooks)
+        try:
+            for dt in (torch.uint8, torch.int64):
+                m, st = q.quicfl_compress(x, nbits, seeds, rots, sender=snd, px_states=states, x_dtype=dt, _state_out=True)
+                assert last_form(H.SENDER, hooks) == (H.ONE_WAVE if hooks else sform)
+                out = q.quicfl_decompress_messages(m, rt)
+                assert last_form(H.RECEIVER, hooks) == (H.ONE_WAVE if hooks else rform)
+                res[hooks, dt] = (m, st, out)
+            res[hooks, "fused"] = q.quicfl_quantize(x, nbits, seeds, rots, sender=snd, recv_table=rt, px_states=states)
+            assert last_form(H.SENDER, hooks) == (H.ONE_WAVE if hooks else sform)
+            if not hooks and sform == H.JUMP:
+                assert H.last_plan(load(), H.SENDER)["two_wave"] == (n == 342)
+                assert rform != H.JUMP or H.last_plan(load(), H.RECEIVER)["two_wave"] == (n == 342)
+        finally:
+            load().uq_test_set_quicfl_hooks(prev)
+    wave = res[2, torch.int64]
+    for dt in (torch.uint8, torch.int64):
+        (a, sa, da), (b, sb, db) = res[0, dt], res[2, dt]
+        _same_messages(a, sa, b, sb)
+        assert torch.equal(da.view(torch.int32), db.view(torch.int32))
+        assert torch.equal(b.X.to(torch.int64), wave[0].X) and torch.equal(db.view(torch.int32), wave[2].view(torch.int32))
+    for hooks in (0, 2):
+        fo, fst, fsc = res[hooks, "fused"]
+        assert torch.equal(fo.view(torch.int32), wave[2].view(torch.int32)), hooks
+        assert np.array_equal(fst, wave[1]) and torch.equal(fsc, wave[0].scale), hooks
+    if oracle is None:
+        return
+    m, st, out = res[0, torch.int64]
+    out = out.cpu().numpy()
+    for j in range(n):
+        exp, gst, rec = oracle[j]
+        assert np.array_equal(m.X[j].cpu().numpy(), exp["X"]), j
+        assert np.array_equal(m.exact_mask[j].cpu().numpy(), exp["exact_indeces"]), j
+        cnt = int(m.exact_count[j])
+        assert m.exact_vals[j, :cnt].cpu().numpy().view(np.uint32).tolist() == exp["exact_values"].view(np.uint32).tolist()
+        assert np.float32(m.scale[j].item()).view(np.uint32) == np.float32(exp["scale"]).view(np.uint32)
+        assert (st[j, 0], st[j, 1]) == (gst[0], gst[1]) and np.array_equal(st[j, 2:], gst[2]), j
+        assert out[j].view(np.uint32).tolist() == rec.view(np.uint32).tolist(), j

@@ -24,6 +24,8 @@ SIGNATURES = {
     "uq_build_id": (ctypes.c_char_p, []),
     "uq_test_force_replay_failure": (ctypes.c_int, [ctypes.c_int]),
     "uq_test_set_quicfl_hooks": (ctypes.c_int, [ctypes.c_int]),
+    "uq_test_quicfl_plan": (ctypes.c_int, [_i32, _i64, _i64, _i32, _i32, _p, _i32]),
+    "uq_test_last_quicfl_plan": (ctypes.c_int, [_i32, _p, _i32]),
     "uq_test_unbiased_plan": (ctypes.c_int, [_i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p,
                                              _i32]),
     "uq_test_last_unbiased_plan": (ctypes.c_int, [_p, _i32]),

@@ -1,4 +1,4 @@
-// uq_quicfl.hip — QUIC-FL: the jump plans, the launchers of uq_quicfl_kernels.h and the C API
+// uq_quicfl.hip — QUIC-FL: the dispatch plan, the launchers of uq_quicfl_kernels.h and the C API
 // of the sender (uq_quicfl_compress_f32, uq_quicfl_quantize_f32) and the receiver
 // (uq_quicfl_receive_*), and uq_xxh64 (the sender's prng seed).  The RHT and the norm run in
 // uq_eden.hip.
@@ -11,86 +11,170 @@
 #include <cstring>
 #include <map>
 #include <mutex>
+#include <optional>
 #include <tuple>
+#include <type_traits>
 #include <vector>
 
 #include "uq_internal.h"
 #include "uq_quicfl_kernels.h"
 
-// test hooks of the QUIC-FL kernels (never set by the library itself): bit 0 makes every run
-// of the few-message team kernels skip its waits and report UQ_QFL_TIMEOUT; bit 1 sends every
-// call to the one-wave-per-message kernels (so a test can compare both forms on one message)
+// uq_test_set_quicfl_hooks (include/uq_dme.h); each entry point loads it once, into its plan
 static std::atomic<int> g_quicfl_hooks{0};
 
-// The jump path (KQ0s + KQ0j + KQ1j + KQ1f, uq_quicfl_kernels.h) for few messages: R runs of L
-// rounds per message, R from a cost model of the phases (measured round-5 constants): the
-// streams (~20 us), the jumps (~tJ of the whole GPU per jump) and a round of passes A + B on one
-// wave (~tR; a run wave per SIMD).  The one-wave kernel when the model gives the jumps no gain.
-struct QflJumpPlan {
-    bool use = false;
-    int32_t R = 0;
-    int64_t L = 0, qL = 0;
+namespace {
+
+// ---- dispatch plan -------------------------------------------------------------------
+// Every decision of a sender or receiver call, made once on the host from (side, n, D, hooks,
+// workspace); DESIGN.md §4.4 has the table.  The launchers launch what the plan names and the
+// workspace sizes read the same function, so the test hooks (uq_test_quicfl_plan,
+// uq_test_last_quicfl_plan) report what a call really runs.
+struct QflPlan {
+    int32_t form = UQ_QFL_FORM_NONE;
+    int32_t R = 0;                  // jump form: R runs of L rounds per message
+    int64_t L = 0, qL = 0;          // qL: block of the sender's first pass-B local word (qfl_ctx)
+    bool w2 = false;                // jump form: more than kQfRunWaves1 run waves, two per SIMD
+    int32_t force_timeout = 0;      // hook bit 0
+    int32_t side = UQ_QFL_SIDE_NONE;   // the sender's work on the side stream
+    size_t jump_bytes = 0;          // the workspace's jump region, whatever the hooks say
 };
 
-// Up to 1024 run waves a wave per SIMD; up to 2048 two (quicfl_send_runs_kernel<., true>), a
-// round then costing ~1.3 tR (round 6, profiles/r6k_* .. r6x_*: 512 x 2^20 compress 12.0 -> 7.6
-// ms, 1024 x 2^20 14.4 -> 12.9 with R = 2 once the runs' pass A moved to the side stream and the
-// counting pass went; 256 x 2^22 round trip 24.2 -> 17.5).
+// What differs between the two sides in the plan: a round of one run wave costs ~tR us, a message
+// takes jmul R - jsub jumps (sender: three blocks per run but run 0's two local ones; receiver:
+// one), the team kernel has `team_runs` run waves, and the jump region holds `streams` streams
+// and `kinds` blocks per run (the sender without the jump form: KQ1a's local blocks, [n][624]).
+struct QflSide {
+    double tR;
+    int64_t jmul, jsub, team_runs;
+    size_t streams, kinds;
+};
+constexpr QflSide kQflSides[2] = {{7.5, 3, 2, kQfRuns, 2, 3}, {3.0, 1, 1, kQrRuns, 1, 1}};
+
+// Up to 1024 run waves a wave per SIMD; up to 2048 two, a round then costing ~1.3 tR.
 constexpr int64_t kQfJumpMaxN = 1024;
 constexpr int64_t kQfRunWaves1 = 1024, kQfRunWaves2 = 2048;
-static QflJumpPlan qfl_jump_plan(int64_t n, int64_t D) {
-    QflJumpPlan p;
+
+// The jump form's R from a cost model of its phases (measured round-5 / round-6 constants, us):
+// the streams (~20), the jumps (~0.12 of the whole GPU each) and L rounds on one wave.  True
+// when the model beats what the call would run otherwise:
+//   sender    up to 128 messages and above 256 the one-wave kernel (~tR per round, 1024 waves at
+//             a time); 129-256 the team kernel at ~2.85 us per round, the model ~1.4x optimistic
+//   receiver  up to 256 messages the team kernel (~1 us per round), above the one-wave kernel
+bool qfl_jump_search(int side, int64_t n, int64_t D, int32_t* R_out, int64_t* L_out) {
+    const QflSide& s = kQflSides[side];
     const int64_t nch = (D + kMtN - 1) / kMtN;
-    if (n < 1 || n > kQfJumpMaxN || nch < 8 || D > ((int64_t)1 << 28)) return p;
-    const double tS = 20.0, tJ = 0.12, tR = 7.5, f2 = 1.3;
+    if (n < 1 || n > kQfJumpMaxN || nch < 8 || D > ((int64_t)1 << 28)) return false;
+    const double tS = 20.0, tJ = 0.12, tR = s.tR, f2 = 1.3;
     double best = 1e300;
     for (int64_t R = 1; R <= 1024 && R <= nch; ++R) {
         const int64_t L = (nch + R - 1) / R, Ru = (nch + L - 1) / L;
         if (Ru != R || n * R > kQfRunWaves2) continue;
-        const double t = tS + (double)(n * (3 * R - 2)) * tJ + (double)L * tR * (n * R > kQfRunWaves1 ? f2 : 1.0);
+        const double t = tS + (double)(n * (s.jmul * R - s.jsub)) * tJ + (double)L * tR * (n * R > kQfRunWaves1 ? f2 : 1.0);
         if (t < best) {
             best = t;
-            p.R = (int32_t)R;
-            p.L = L;
+            *R_out = (int32_t)R;
+            *L_out = L;
         }
     }
-    // against: up to 128 messages the team kernel as round 5 measured it; 129-256 the team kernel
-    // at ~2.85 us per round, the model ~1.4x optimistic (r6l: 256 x 2^20 team 5.5 / jump 5.9 ms,
-    // 2^21 11.3 / 10.3, 2^22 round trip 24.3 / 18.7); above, a wave per message
-    if (n <= 128 || n > kQfTeamMaxN)
-        p.use = best < 0.8 * (double)((n + 1023) / 1024) * (double)nch * tR;
-    else
-        p.use = best < 2.0 * (double)nch;
-    p.qL = ((int64_t)kMtN + D) / kMtN;               // block of the first pass-B local word (qfl_ctx)
+    if (side == UQ_QFL_RECEIVER) return best < 0.8 * (double)nch * (n <= kQfTeamMaxN ? 1.0 : tR);
+    if (n <= 128 || n > kQfTeamMaxN) return best < 0.8 * (double)((n + 1023) / 1024) * (double)nch * tR;
+    return best < 2.0 * (double)nch;
+}
+
+// ws_avail: bytes the caller gives the jump region.  The receiver runs without one; the sender's
+// entry points refuse a workspace smaller than the plan's, so they plan with SIZE_MAX.
+QflPlan qfl_plan(int side, int64_t n, int64_t D, int hooks, size_t ws_avail) {
+    const QflSide& s = kQflSides[side];
+    QflPlan p;
+    const bool wins = qfl_jump_search(side, n, D, &p.R, &p.L);
+    if (wins)
+        p.jump_bytes = ((size_t)n * s.streams * kMjX + (size_t)n * p.R * (s.kinds * kMjParts * kMtN + 2)) * sizeof(uint32_t);
+    else if (side == UQ_QFL_SENDER)
+        p.jump_bytes = (size_t)std::max<int64_t>(n, 0) * kMtN * sizeof(uint32_t);
+    if (n < 1 || D < 1) return p;
+    p.force_timeout = hooks & 1;
+    if (wins && !(hooks & 7) && ws_avail >= p.jump_bytes) {
+        p.form = UQ_QFL_FORM_JUMP;
+        p.qL = ((int64_t)kMtN + D) / kMtN;
+        p.w2 = n * p.R > kQfRunWaves1;
+    } else {
+        const bool team = !(hooks & 2) && n <= kQfTeamMaxN && D >= (int64_t)kMtN * s.team_runs && D <= kQfTeamMaxD;
+        p.form = team ? UQ_QFL_FORM_TEAM : UQ_QFL_FORM_ONE_WAVE;
+        p.R = 0;
+        p.L = 0;
+    }
+    if (side == UQ_QFL_SENDER)
+        p.side = p.form == UQ_QFL_FORM_JUMP ? UQ_QFL_SIDE_JUMP
+                                             : p.form == UQ_QFL_FORM_ONE_WAVE ? UQ_QFL_SIDE_PASS_A : UQ_QFL_SIDE_NONE;
     return p;
 }
 
-// The receiver's jump path: one stream, one jump per run; a round (one wave: the h word, the
-// table gather, X, the mask and the exact value) ~tR, ~1.3 tR at two waves per SIMD (more than
-// 1024 run waves; 512 x 2^20 decompress 5.60 -> 3.53 ms, 1024 x 2^20 7.4 -> 6.4, profiles/r6r_*,
-// r6w_*, r6x_*).  Taken when it beats the team kernel (~1 us per round of the h scout's twists
-// and the runs behind it).
-static QflJumpPlan qfl_recv_jump_plan(int64_t n, int64_t D) {
-    QflJumpPlan p;
-    const int64_t nch = (D + kMtN - 1) / kMtN;
-    if (n < 1 || n > kQfJumpMaxN || nch < 8 || D > ((int64_t)1 << 28)) return p;
-    const double tS = 20.0, tJ = 0.12, tR = 3.0;
-    double best = 1e300;
-    for (int64_t R = 1; R <= 1024 && R <= nch; ++R) {
-        const int64_t L = (nch + R - 1) / R, Ru = (nch + L - 1) / L;
-        if (Ru != R || n * R > kQfRunWaves2) continue;                 // (its kernels fit 2 waves per SIMD)
-        const double t = tS + (double)(n * (R - 1)) * tJ + (double)L * tR * (n * R > kQfRunWaves1 ? 1.3 : 1.0);
-        if (t < best) {
-            best = t;
-            p.R = (int32_t)R;
-            p.L = L;
-        }
-    }
-    // against the team kernel (~1 us per round) up to 256 messages, a wave per message (~tR per
-    // round, one wave per SIMD) above
-    p.use = best < 0.8 * (double)nch * (n <= kQfTeamMaxN ? 1.0 : tR);
-    return p;
+thread_local QflPlan t_last_plan[2];         // uq_test_last_quicfl_plan, per side
+
+int export_plan(const QflPlan& p, int64_t* out, int32_t cap) {
+    if (!out || cap < 0) return fail(UQ_E_INVALID, "null plan output");
+    const int64_t f[UQ_QFL_PLAN_FIELDS] = {p.form, p.R, p.L, p.w2, p.force_timeout, p.side};
+    for (int i = 0; i < std::min<int32_t>(cap, UQ_QFL_PLAN_FIELDS); ++i) out[i] = f[i];
+    return UQ_OK;
 }
+
+// ---- kernel selection and launch shapes ------------------------------------------------
+// The run-time x_kind (0 int64, 1 uint8, 2 int32 / the sender's fused instances) becomes a
+// compile-time constant: f(XK) launches the instance it names; with W2 behind it for the
+// sender's runs.  (2, 0, 1 is the order the sender's instances have always been emitted in;
+// another order moves the padding between kernels, and with it tools/kernel_table.py's hashes.)
+template <int K>
+using Xk = std::integral_constant<int, K>;
+template <bool B>
+using Flag = std::integral_constant<bool, B>;
+
+template <class F>
+void select_xk(int32_t x_kind, F&& f) {
+    if (x_kind == 2) f(Xk<2>{});
+    else if (x_kind == 0) f(Xk<0>{});
+    else f(Xk<1>{});
+}
+template <class F>
+void select_xk_w2(int32_t x_kind, bool w2, F&& f) {
+    if (w2) select_xk(x_kind, [&](auto XK) { f(XK, Flag<true>{}); });
+    else select_xk(x_kind, [&](auto XK) { f(XK, Flag<false>{}); });
+}
+
+const dim3 kWaveBlock(64 * kQfWavesPerWG), kTeamBlock(64 * kQfTeamWaves);
+dim3 wave_grid(int64_t waves) { return dim3((unsigned)((waves + kQfWavesPerWG - 1) / kQfWavesPerWG)); }
+int launched(const char* what) { return hip_check(hipGetLastError(), what); }
+
+// ---- side stream -----------------------------------------------------------------------
+// Forks the thread's side stream from st; join() records the side stream's end and makes st
+// wait for it.  The destructor joins if that has not happened, so once forked the caller's
+// stream waits on every exit path: the side kernels write into the caller's workspace, which
+// may be freed or reused after an early error return.
+class SideFork {
+public:
+    SideFork(hipStream_t st, int* rc) : st_(st) {
+        if ((*rc = side_stream(&sb_))) return;
+        if ((*rc = hip_check(hipEventRecord(sb_->fork, st), "record fork"))) return;
+        if ((*rc = hip_check(hipStreamWaitEvent(sb_->s, sb_->fork, 0), "wait fork"))) return;
+        open_ = true;
+    }
+    SideFork(const SideFork&) = delete;
+    SideFork& operator=(const SideFork&) = delete;
+    ~SideFork() { (void)join(); }
+    hipStream_t side() const { return sb_->s; }
+    int join() {
+        if (!open_) return UQ_OK;
+        open_ = false;
+        const int rc = hip_check(hipEventRecord(sb_->join, sb_->s), "record join");
+        return rc ? rc : hip_check(hipStreamWaitEvent(st_, sb_->join, 0), "wait join");
+    }
+
+private:
+    hipStream_t st_;
+    SideStream* sb_ = nullptr;
+    bool open_ = false;
+};
+
+}  // namespace
 
 extern "C" {
 
@@ -98,9 +182,21 @@ int uq_mtpoly_progression(int64_t b0, int64_t step, int32_t count, uint32_t* out
 
 int uq_test_set_quicfl_hooks(int flags) { return g_quicfl_hooks.exchange(flags & 7); }
 
+int uq_test_quicfl_plan(int32_t side, int64_t n, int64_t D, int32_t hooks, int32_t has_ws, int64_t* plan_out,
+                        int32_t cap) {
+    if (side != UQ_QFL_SENDER && side != UQ_QFL_RECEIVER) return fail(UQ_E_INVALID, "side must be 0 (sender) or 1 (receiver)");
+    if (n < 0 || D < 0) return fail(UQ_E_INVALID, "n and D must be >= 0");
+    return export_plan(qfl_plan(side, n, D, hooks & 7, has_ws ? SIZE_MAX : 0), plan_out, cap);
+}
+
+int uq_test_last_quicfl_plan(int32_t side, int64_t* plan_out, int32_t cap) {
+    if (side != UQ_QFL_SENDER && side != UQ_QFL_RECEIVER) return fail(UQ_E_INVALID, "side must be 0 (sender) or 1 (receiver)");
+    return export_plan(t_last_plan[side], plan_out, cap);
+}
+
 // t^(624 b) mod phi for the plan's run starts, on the device, cached per (device, qL, L, R):
 // rows [0, R) = polyA (row r: b = r L - 1; row 0 unused), rows [R, 2R) = polyB (b = qL + r L - 1)
-static int qfl_jump_polys(const QflJumpPlan& p, bool a_only, const uint32_t** out) {
+static int qfl_jump_polys(const QflPlan& p, bool a_only, const uint32_t** out) {
     static std::mutex mu;
     static std::map<std::tuple<int, int64_t, int64_t, int32_t>, uint32_t*> cache;
     int dev = 0;
@@ -133,8 +229,7 @@ static int qfl_jump_polys(const QflJumpPlan& p, bool a_only, const uint32_t** ou
     return UQ_OK;
 }
 
-static int quicfl_recv_jump(const QflRecvArgs& r, int32_t x_kind, const QflJumpPlan& jp, char* wsb, hipStream_t st);
-
+// ---- QUIC-FL receiver --------------------------------------------------------------------
 int uq_quicfl_receive_f32(const void* X, int32_t x_kind, int64_t n, int64_t D, const float* recv_table,
                           int32_t table_rows, int32_t h_len, const int32_t* prng_seeds, const uint8_t* exact_mask,
                           const float* exact_vals, int32_t exact_layout, const int32_t* exact_count, const float* scale,
@@ -146,15 +241,53 @@ int uq_quicfl_receive_f32(const void* X, int32_t x_kind, int64_t n, int64_t D, c
 int uq_quicfl_receive_workspace_bytes(int64_t n, int64_t D, size_t* bytes_out) {
     if (!bytes_out) return fail(UQ_E_INVALID, "null bytes_out");
     if (n < 0 || D < 0) return fail(UQ_E_INVALID, "n and D must be >= 0");
-    const QflJumpPlan p = qfl_recv_jump_plan(n, D);
-    *bytes_out = p.use ? ((size_t)n * kMjX + (size_t)n * p.R * (kMjParts * kMtN + 2)) * sizeof(uint32_t) : 0;
+    *bytes_out = qfl_plan(UQ_QFL_RECEIVER, n, D, 0, 0).jump_bytes;
     return UQ_OK;
+}
+
+// KQ0s + KQ0j (the h stream, one block per run) + KQ2c + KQ2j + KQ2f
+static int quicfl_recv_jump(const QflRecvArgs& r, int32_t x_kind, const QflPlan& P, char* wsb, hipStream_t st) {
+    const int64_t n = r.n;
+    const uint32_t* polys = nullptr;
+    int rc = qfl_jump_polys(P, true, &polys);
+    if (rc) return rc;
+    uint32_t* xs = (uint32_t*)wsb;
+    uint32_t* parts = xs + (size_t)n * kMjX;
+    QflJumpArgs ja{};
+    ja.prng_seeds = r.prng_seeds;
+    ja.polyA = polys;
+    ja.polyB = polys;                                    // (unused: one kind)
+    ja.xs = xs;
+    ja.parts = parts;
+    ja.R = P.R;
+    ja.n = n;
+    ja.nstreams = 1;
+    ja.kinds = 1;
+    hipLaunchKernelGGL(quicfl_stream_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, ja);
+    if ((rc = launched("quicfl_stream_kernel launch"))) return rc;
+    hipLaunchKernelGGL(quicfl_jump_kernel, dim3((unsigned)(n * P.R * kMjParts)), dim3(256), 0, st, ja);
+    if ((rc = launched("quicfl_jump_kernel launch"))) return rc;
+    QflRunArgs ra{};
+    ra.parts = parts;
+    ra.runinfo = (int32_t*)(parts + (size_t)n * P.R * kMjParts * kMtN);
+    ra.R = P.R;
+    ra.L = P.L;
+    hipLaunchKernelGGL(quicfl_recv_count_kernel, wave_grid(n * P.R), kWaveBlock, 0, st, r, ra);
+    if ((rc = launched("quicfl_recv_count_kernel launch"))) return rc;
+    select_xk(x_kind, [&](auto XK) {
+        hipLaunchKernelGGL(quicfl_recv_runs_kernel<XK()>, wave_grid(n * P.R), kWaveBlock, 0, st, r, ra);
+    });
+    if ((rc = launched("quicfl_recv_runs_kernel launch"))) return rc;
+    hipLaunchKernelGGL(quicfl_recv_fin_kernel, wave_grid(n), kWaveBlock, 0, st, r, ra);
+    return launched("quicfl_recv_fin_kernel launch");
 }
 
 int uq_quicfl_receive_ws_f32(const void* X, int32_t x_kind, int64_t n, int64_t D, const float* recv_table,
                              int32_t table_rows, int32_t h_len, const int32_t* prng_seeds, const uint8_t* exact_mask,
                              const float* exact_vals, int32_t exact_layout, const int32_t* exact_count,
                              const float* scale, float* out, int32_t* info, void* ws, size_t ws_bytes, void* stream) {
+    const int hooks = g_quicfl_hooks.load();
+    t_last_plan[UQ_QFL_RECEIVER] = QflPlan{};
     if (n < 0 || D < 0) return fail(UQ_E_INVALID, "n and D must be >= 0");
     if (n > 65535) return fail(UQ_E_INVALID, "at most 65535 clients per call");
     if (D > ((int64_t)1 << 28)) return fail(UQ_E_INVALID, "at most 2^28 coordinates per message");
@@ -166,6 +299,8 @@ int uq_quicfl_receive_ws_f32(const void* X, int32_t x_kind, int64_t n, int64_t D
     if (h_len < 1 || table_rows < 1 || (int64_t)h_len * table_rows > kQflTab)
         return fail(UQ_E_INVALID, "receiver table must hold 1..1024 entries");
     hipStream_t st = (hipStream_t)stream;
+    const QflPlan P = qfl_plan(UQ_QFL_RECEIVER, n, D, hooks, ws ? ws_bytes : 0);
+    t_last_plan[UQ_QFL_RECEIVER] = P;
     QflRecvArgs r{};
     r.X = X;
     r.n = n;
@@ -181,65 +316,16 @@ int uq_quicfl_receive_ws_f32(const void* X, int32_t x_kind, int64_t n, int64_t D
     r.scale = scale;
     r.out = out;
     r.info = info;
-    const int hooks = g_quicfl_hooks.load();
-    r.force_timeout = hooks & 1;
-    // few messages: every run at once from jumped blocks of the h stream (given a workspace), or
-    // a workgroup per message (the h stream's scout + 7 runs); batches: a wave each
-    const QflJumpPlan jp = qfl_recv_jump_plan(n, D);
-    size_t need = 0;
-    (void)uq_quicfl_receive_workspace_bytes(n, D, &need);
-    if (!(hooks & 7) && jp.use && ws && ws_bytes >= need) return quicfl_recv_jump(r, x_kind, jp, (char*)ws, st);
-    if (!(hooks & 2) && n <= kQfTeamMaxN && D >= (int64_t)kMtN * kQrRuns && D <= kQfTeamMaxD) {
-        const dim3 grid((unsigned)n), block(64 * kQfTeamWaves);
-        if (x_kind == 0) hipLaunchKernelGGL(quicfl_recv_team_kernel<0>, grid, block, 0, st, r);
-        else if (x_kind == 1) hipLaunchKernelGGL(quicfl_recv_team_kernel<1>, grid, block, 0, st, r);
-        else hipLaunchKernelGGL(quicfl_recv_team_kernel<2>, grid, block, 0, st, r);
-        return hip_check(hipGetLastError(), "quicfl_recv_team_kernel launch");
+    r.force_timeout = P.force_timeout;
+    if (P.form == UQ_QFL_FORM_JUMP) return quicfl_recv_jump(r, x_kind, P, (char*)ws, st);
+    if (P.form == UQ_QFL_FORM_TEAM) {
+        select_xk(x_kind, [&](auto XK) {
+            hipLaunchKernelGGL(quicfl_recv_team_kernel<XK()>, dim3((unsigned)n), kTeamBlock, 0, st, r);
+        });
+        return launched("quicfl_recv_team_kernel launch");
     }
-    const dim3 grid((unsigned)((n + kQfWavesPerWG - 1) / kQfWavesPerWG)), block(64 * kQfWavesPerWG);
-    if (x_kind == 0) hipLaunchKernelGGL(quicfl_recv_wave_kernel<0>, grid, block, 0, st, r);
-    else if (x_kind == 1) hipLaunchKernelGGL(quicfl_recv_wave_kernel<1>, grid, block, 0, st, r);
-    else hipLaunchKernelGGL(quicfl_recv_wave_kernel<2>, grid, block, 0, st, r);
-    return hip_check(hipGetLastError(), "quicfl_recv_wave_kernel launch");
-}
-
-// KQ0s + KQ0j (the h stream, one block per run) + KQ2c + KQ2j + KQ2f
-static int quicfl_recv_jump(const QflRecvArgs& r, int32_t x_kind, const QflJumpPlan& jp, char* wsb, hipStream_t st) {
-    const int64_t n = r.n;
-    const uint32_t* polys = nullptr;
-    int rc = qfl_jump_polys(jp, true, &polys);
-    if (rc) return rc;
-    uint32_t* xs = (uint32_t*)wsb;
-    uint32_t* parts = xs + (size_t)n * kMjX;
-    QflJumpArgs ja{};
-    ja.prng_seeds = r.prng_seeds;
-    ja.polyA = polys;
-    ja.polyB = polys;                                    // (unused: one kind)
-    ja.xs = xs;
-    ja.parts = parts;
-    ja.R = jp.R;
-    ja.n = n;
-    ja.nstreams = 1;
-    ja.kinds = 1;
-    hipLaunchKernelGGL(quicfl_stream_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, ja);
-    if ((rc = hip_check(hipGetLastError(), "quicfl_stream_kernel launch"))) return rc;
-    hipLaunchKernelGGL(quicfl_jump_kernel, dim3((unsigned)(n * jp.R * kMjParts)), dim3(256), 0, st, ja);
-    if ((rc = hip_check(hipGetLastError(), "quicfl_jump_kernel launch"))) return rc;
-    QflRunArgs ra{};
-    ra.parts = parts;
-    ra.runinfo = (int32_t*)(parts + (size_t)n * jp.R * kMjParts * kMtN);
-    ra.R = jp.R;
-    ra.L = jp.L;
-    const dim3 rgrid((unsigned)((n * jp.R + kQfWavesPerWG - 1) / kQfWavesPerWG)), blk(64 * kQfWavesPerWG);
-    hipLaunchKernelGGL(quicfl_recv_count_kernel, rgrid, blk, 0, st, r, ra);
-    if ((rc = hip_check(hipGetLastError(), "quicfl_recv_count_kernel launch"))) return rc;
-    if (x_kind == 0) hipLaunchKernelGGL(quicfl_recv_runs_kernel<0>, rgrid, blk, 0, st, r, ra);
-    else if (x_kind == 1) hipLaunchKernelGGL(quicfl_recv_runs_kernel<1>, rgrid, blk, 0, st, r, ra);
-    else hipLaunchKernelGGL(quicfl_recv_runs_kernel<2>, rgrid, blk, 0, st, r, ra);
-    if ((rc = hip_check(hipGetLastError(), "quicfl_recv_runs_kernel launch"))) return rc;
-    hipLaunchKernelGGL(quicfl_recv_fin_kernel, dim3((unsigned)((n + kQfWavesPerWG - 1) / kQfWavesPerWG)), blk, 0, st, r,
-                       ra);
-    return hip_check(hipGetLastError(), "quicfl_recv_fin_kernel launch");
+    select_xk(x_kind, [&](auto XK) { hipLaunchKernelGGL(quicfl_recv_wave_kernel<XK()>, wave_grid(n), kWaveBlock, 0, st, r); });
+    return launched("quicfl_recv_wave_kernel launch");
 }
 
 int uq_quicfl_prepare_f32(const int32_t* X, int64_t n, int64_t D, const float* recv_table, int32_t table_rows,
@@ -250,153 +336,180 @@ int uq_quicfl_prepare_f32(const int32_t* X, int64_t n, int64_t D, const float* r
 }
 
 // ---- QUIC-FL sender ----------------------------------------------------------------------
-// Workspace: the EDEN layout (rotated vectors, norms, segmented-norm region) + h [n][D] u8 +
-// the jump path's blocks [n][R][3][624] u32 and run records [n][R][2] i32.
+// Workspace: the EDEN layout (rotated vectors, norms, segmented-norm region) + h [n][D] u8 + the
+// plan's jump region: streams [n][2][kMjX], parts [n][R][3][kMjParts][624], run records
+// [n][R][2] (without the jump form: the local blocks after KQ1a, [n][624]).
 static size_t quicfl_h_off(int64_t n, int64_t dim) {
     return up256(rht_layout(n, dim).total);
 }
 static size_t quicfl_jump_off(int64_t n, int64_t dim) {
     return up256(quicfl_h_off(n, dim) + (size_t)n * (size_t)rht_layout(n, dim).D);
 }
-// jump region: streams [n][2][kMjX], parts [n][R][3][kMjParts][624], run records [n][R][2]
-// (without the jump path: the local blocks after KQ1a, [n][624])
-static size_t quicfl_ws_total(int64_t n, int64_t dim) {
-    const QflJumpPlan p = qfl_jump_plan(n, rht_layout(n, dim).D);
-    const size_t jb = p.use ? ((size_t)n * 2 * kMjX + (size_t)n * p.R * (3 * kMjParts * kMtN + 2)) * sizeof(uint32_t)
-                            : (size_t)n * kMtN * sizeof(uint32_t);
-    return quicfl_jump_off(n, dim) + jb;
-}
 
 int uq_quicfl_workspace_bytes(int64_t n, int64_t dim, size_t* bytes_out) {
     if (!bytes_out) return fail(UQ_E_INVALID, "null bytes_out");
     if (n < 0 || dim < 0) return fail(UQ_E_INVALID, "n and dim must be >= 0");
-    *bytes_out = quicfl_ws_total(n, dim);
+    *bytes_out = quicfl_jump_off(n, dim) + qfl_plan(UQ_QFL_SENDER, n, rht_layout(n, dim).D, 0, 0).jump_bytes;
     return UQ_OK;
 }
 
-// The jump path's first two phases (KQ0s + KQ0j) depend only on the generators, so they are
-// issued first, on the side stream, and run beside the RHT and the norm on the caller's stream
-// (~80 us of small kernels for one 2^20 message); the runs wait for them.
-struct QflJumpLaunch {
-    bool use = false;
-    bool passa = false;             // KQ1a runs on the side stream instead (the one-wave form)
-    bool passa_runs = false;        // KQ1ar ran every run's pass A on the side stream (the jump path)
-    QflJumpPlan jp;
-    uint32_t* parts = nullptr;
-    uint32_t* lstate = nullptr;     // KQ1a's local blocks
-    SideStream* sb = nullptr;
-};
-// Which sender form a call takes (launch_quicfl_send): 0 the jump path, 1 the team kernel
-// (KQ1t), 2 the one-wave kernel (KQ1).
-static int qfl_send_form(int64_t n, int64_t D, bool jump_use) {
-    const int hooks = g_quicfl_hooks.load();
-    if (jump_use) return 0;
-    const QflJumpPlan jp = qfl_jump_plan(n, D);
-    if (!(hooks & 2) && ((hooks & 5) || !jp.use) && n <= kQfTeamMaxN && D >= (int64_t)kMtN * kQfRuns &&
-        D <= kQfTeamMaxD)
-        return 1;
-    return 2;
-}
-static int quicfl_jump_fork(int64_t n, int64_t D, int64_t dim, const int32_t* prng_seeds, const uint32_t* px_state,
-                            const int32_t* px_seeds, int32_t h_len, char* wsb, hipStream_t st, QflJumpLaunch* jl) {
-    *jl = QflJumpLaunch{};
-    const int hooks = g_quicfl_hooks.load();
-    const QflJumpPlan jp = qfl_jump_plan(n, D);
-    if ((hooks & 7) || !jp.use) {
-        if (qfl_send_form(n, D, false) != 2) return UQ_OK;
-        // the one-wave form: its pass A (h from the message seeds) beside the RHT and the norm
-        SideStream* sb = nullptr;
-        int rc = side_stream(&sb);
-        if (rc) return rc;
-        if ((rc = hip_check(hipEventRecord(sb->fork, st), "record fork"))) return rc;
-        if ((rc = hip_check(hipStreamWaitEvent(sb->s, sb->fork, 0), "wait fork"))) return rc;
-        QflSendArgs qa{};
-        qa.prng_seeds = prng_seeds;
-        qa.hbuf = (uint8_t*)(wsb + quicfl_h_off(n, dim));
-        qa.h_len = h_len;
-        qa.D = D;
-        qa.n = n;
-        uint32_t* ls = (uint32_t*)(wsb + quicfl_jump_off(n, dim));
-        hipLaunchKernelGGL(quicfl_pass_a_kernel, dim3((unsigned)((n + kQfWavesPerWG - 1) / kQfWavesPerWG)),
-                           dim3(64 * kQfWavesPerWG), 0, sb->s, qa, ls);
-        rc = hip_check(hipGetLastError(), "quicfl_pass_a_kernel launch");
-        const int rj = hip_check(hipEventRecord(sb->join, sb->s), "record join");
-        if (!rj) {
-            jl->passa = true;                   // the guard and the wave launch wait on the join
-            jl->lstate = ls;
-            jl->sb = sb;
-        } else if (hipEventRecord(sb->join, sb->s) == hipSuccess) {
-            (void)hipStreamWaitEvent(st, sb->join, 0);
-        }
-        return rc ? rc : rj;
+// What the plan sends to the side stream, to run beside the RHT and the norm on the caller's
+// stream: the one-wave form's pass A (KQ1a: h from the message seeds, leaving each local block
+// in the jump region), or the jump form's phases that depend only on the generators (KQ0s +
+// KQ0j, ~80 us of small kernels for one 2^20 message, then KQ1ar: every run's pass A).
+// q: the generators, hbuf, h_len, D and n are set.
+static int quicfl_send_side(const QflSendArgs& q, const QflPlan& P, const uint32_t* polys, uint32_t* jump,
+                            hipStream_t side) {
+    const int64_t n = q.n;
+    QflSendArgs qa{};                                    // what pass A reads
+    qa.prng_seeds = q.prng_seeds;
+    qa.hbuf = q.hbuf;
+    qa.h_len = q.h_len;
+    qa.D = q.D;
+    qa.n = n;
+    if (P.side == UQ_QFL_SIDE_PASS_A) {
+        hipLaunchKernelGGL(quicfl_pass_a_kernel, wave_grid(n), kWaveBlock, 0, side, qa, jump);
+        return launched("quicfl_pass_a_kernel launch");
     }
-    const uint32_t* polys = nullptr;
-    int rc = qfl_jump_polys(jp, false, &polys);
-    if (rc) return rc;
-    SideStream* sb = nullptr;
-    if ((rc = side_stream(&sb))) return rc;
-    if ((rc = hip_check(hipEventRecord(sb->fork, st), "record fork"))) return rc;
-    if ((rc = hip_check(hipStreamWaitEvent(sb->s, sb->fork, 0), "wait fork"))) return rc;
-    auto join_on_error = [&](int err) {      // whatever reached the side stream finishes before st moves on
-        if (hipEventRecord(sb->join, sb->s) == hipSuccess) (void)hipStreamWaitEvent(st, sb->join, 0);
-        return err;
-    };
-    uint32_t* xs = (uint32_t*)(wsb + quicfl_jump_off(n, dim));
-    uint32_t* parts = xs + (size_t)n * 2 * kMjX;
     QflJumpArgs ja{};
-    ja.prng_seeds = prng_seeds;
-    ja.px_state = px_state;
-    ja.px_seeds = px_seeds;
+    ja.prng_seeds = q.prng_seeds;
+    ja.px_state = q.px_state;
+    ja.px_seeds = q.px_seeds;
     ja.polyA = polys;
-    ja.polyB = polys + (size_t)jp.R * kMtN;
-    ja.xs = xs;
-    ja.parts = parts;
-    ja.R = jp.R;
+    ja.polyB = polys + (size_t)P.R * kMtN;
+    ja.xs = jump;
+    ja.parts = jump + (size_t)n * 2 * kMjX;
+    ja.R = P.R;
     ja.n = n;
     ja.nstreams = 2;
     ja.kinds = 3;
-    hipLaunchKernelGGL(quicfl_stream_kernel, dim3((unsigned)((2 * n + 3) / 4)), dim3(256), 0, sb->s, ja);
-    if ((rc = hip_check(hipGetLastError(), "quicfl_stream_kernel launch"))) return join_on_error(rc);
-    hipLaunchKernelGGL(quicfl_jump_kernel, dim3((unsigned)(n * jp.R * 3 * kMjParts)), dim3(256), 0, sb->s, ja);
-    if ((rc = hip_check(hipGetLastError(), "quicfl_jump_kernel launch"))) return join_on_error(rc);
-    {   // KQ1ar: the runs' pass A (h) beside the RHT and the norm
-        QflSendArgs qa{};
-        qa.prng_seeds = prng_seeds;
-        qa.hbuf = (uint8_t*)(wsb + quicfl_h_off(n, dim));
-        qa.h_len = h_len;
-        qa.D = D;
-        qa.n = n;
-        QflRunArgs ra{};
-        ra.parts = parts;
-        ra.R = jp.R;
-        ra.L = jp.L;
-        hipLaunchKernelGGL(quicfl_pass_a_runs_kernel, dim3((unsigned)((n * jp.R + kQfWavesPerWG - 1) / kQfWavesPerWG)),
-                           dim3(64 * kQfWavesPerWG), 0, sb->s, qa, ra);
-        if ((rc = hip_check(hipGetLastError(), "quicfl_pass_a_runs_kernel launch"))) return join_on_error(rc);
-    }
-    if ((rc = hip_check(hipEventRecord(sb->join, sb->s), "record join"))) return join_on_error(rc);
-    jl->use = true;
-    jl->passa_runs = true;
-    jl->jp = jp;
-    jl->parts = parts;
-    jl->sb = sb;
-    return UQ_OK;
+    hipLaunchKernelGGL(quicfl_stream_kernel, dim3((unsigned)((2 * n + 3) / 4)), dim3(256), 0, side, ja);
+    int rc = launched("quicfl_stream_kernel launch");
+    if (rc) return rc;
+    hipLaunchKernelGGL(quicfl_jump_kernel, dim3((unsigned)(n * P.R * 3 * kMjParts)), dim3(256), 0, side, ja);
+    if ((rc = launched("quicfl_jump_kernel launch"))) return rc;
+    QflRunArgs ra{};
+    ra.parts = ja.parts;
+    ra.R = P.R;
+    ra.L = P.L;
+    hipLaunchKernelGGL(quicfl_pass_a_runs_kernel, wave_grid(n * P.R), kWaveBlock, 0, side, qa, ra);
+    return launched("quicfl_pass_a_runs_kernel launch");
 }
 
-static int launch_quicfl_send(QflSendArgs& q, int32_t x_kind, const QflJumpLaunch& jl, hipStream_t st);
-
-// Once the fork has happened, the caller's stream waits on the side stream's join on every exit
-// path: KQ0s / KQ0j write into the caller's workspace, which may be freed or reused after an
-// early error return.  (Waiting twice on the join is harmless.)
-namespace {
-struct QflJoinGuard {
-    const QflJumpLaunch& jl;
-    hipStream_t st;
-    ~QflJoinGuard() {
-        if (jl.use || jl.passa) (void)hipStreamWaitEvent(st, jl.sb->join, 0);
+// The plan's form on the caller's stream, after the join: KQ1j + KQ1f (every run of every message
+// at once from the jumped blocks), KQ1t (scouts + runs in one workgroup per message) or KQ1 (a
+// wave per message).  x_kind 2: the fused instances.
+static int launch_quicfl_send(QflSendArgs& q, int32_t x_kind, const QflPlan& P, uint32_t* jump, hipStream_t st) {
+    const int64_t n = q.n;
+    if (P.form == UQ_QFL_FORM_JUMP) {
+        QflRunArgs ra{};
+        ra.parts = jump + (size_t)n * 2 * kMjX;
+        ra.runinfo = (int32_t*)(ra.parts + (size_t)n * P.R * 3 * kMjParts * kMtN);
+        ra.R = P.R;
+        ra.L = P.L;
+        ra.passa_done = 1;                               // KQ1ar, on the side stream
+        select_xk_w2(x_kind, P.w2, [&](auto XK, auto W2) {
+            hipLaunchKernelGGL((quicfl_send_runs_kernel<XK(), W2()>), wave_grid(n * P.R), kWaveBlock, 0, st, q, ra);
+        });
+        const int rc = launched("quicfl_send_runs_kernel launch");
+        if (rc) return rc;
+        hipLaunchKernelGGL(quicfl_send_fin_kernel, wave_grid(n), kWaveBlock, 0, st, q, ra);
+        return launched("quicfl_send_fin_kernel launch");
     }
+    if (P.form == UQ_QFL_FORM_TEAM) {
+        select_xk(x_kind, [&](auto XK) {
+            hipLaunchKernelGGL(quicfl_send_team_kernel<XK()>, dim3((unsigned)n), kTeamBlock, 0, st, q);
+        });
+        return launched("quicfl_send_team_kernel launch");
+    }
+    q.lstate = jump;                                     // KQ1a's local blocks
+    select_xk(x_kind, [&](auto XK) { hipLaunchKernelGGL(quicfl_send_wave_kernel<XK()>, wave_grid(n), kWaveBlock, 0, st, q); });
+    return launched("quicfl_send_wave_kernel launch");
+}
+
+// The arguments uq_quicfl_compress_f32 and uq_quicfl_quantize_f32 share.
+struct QflSendCall {
+    const float* x;
+    int64_t n, dim;
+    const int8_t* signs;
+    const int32_t* sign_row;
+    const float* table_xp;
+    const uint32_t* table_packed;
+    int64_t table_numel;
+    int32_t h_len;
+    float delta;
+    const int32_t* prng_seeds;
+    const uint32_t* px_state;
+    const int32_t* px_seeds;
+    uint32_t* px_state_out;
+    float* scale;
+    int32_t* info;
+    void* ws;
+    size_t ws_bytes;
+    void* stream;
 };
-}  // namespace
+
+// The sender of both entry points: the shared checks, the plan, the side-stream work, the RHT
+// and the norm (AS:460-470), and the plan's form.  q arrives with the entry point's own fields;
+// own_error / own_null: its own argument check and null pointers, reported in the entry points'
+// order.  *rot: the rotated vectors (null when nothing ran), into which a fused call
+// (q.rtab set) also writes the receiver's values.
+static int quicfl_send(const QflSendCall& c, const char* own_error, bool own_null, QflSendArgs q, int32_t x_kind,
+                       float** rot) {
+    const int hooks = g_quicfl_hooks.load();
+    t_last_plan[UQ_QFL_SENDER] = QflPlan{};
+    *rot = nullptr;
+    const int64_t n = c.n, dim = c.dim;
+    if (n < 0 || dim < 0) return fail(UQ_E_INVALID, "n and dim must be >= 0");
+    if (n > 65535) return fail(UQ_E_INVALID, "at most 65535 messages per call");
+    if (dim > ((int64_t)1 << 28)) return fail(UQ_E_INVALID, "dim must be <= 2^28");
+    if (c.h_len < 1 || c.h_len > 256) return fail(UQ_E_INVALID, "h_len must be 1..256");
+    if (c.table_numel < c.h_len || c.table_numel % c.h_len) return fail(UQ_E_INVALID, "table_numel must be a multiple of h_len");
+    if (c.table_numel >= ((int64_t)1 << 24)) return fail(UQ_E_INVALID, "table_numel must be below 2^24");
+    if (own_error) return fail(UQ_E_INVALID, own_error);
+    if (n == 0 || dim == 0) return UQ_OK;
+    if (own_null || !c.x || !c.signs || !c.table_xp || !c.prng_seeds || !c.info) return fail(UQ_E_INVALID, "null pointer");
+    if (!c.px_state && !c.px_seeds) return fail(UQ_E_INVALID, "px_state or px_seeds is required");
+    const RhtLayout w = rht_layout(n, dim);
+    const size_t joff = quicfl_jump_off(n, dim);
+    const QflPlan P = qfl_plan(UQ_QFL_SENDER, n, w.D, hooks, SIZE_MAX);
+    if (!c.ws || c.ws_bytes < joff + P.jump_bytes) return fail(UQ_E_WORKSPACE, "workspace too small");
+    t_last_plan[UQ_QFL_SENDER] = P;
+    hipStream_t st = (hipStream_t)c.stream;
+    char* wsb = (char*)c.ws;
+    uint32_t* jump = (uint32_t*)(wsb + joff);
+    q.tab = (const float2*)c.table_xp;
+    q.tabp = c.table_packed;
+    q.numel = c.table_numel;
+    q.half = ((c.table_numel / c.h_len) - 1) * c.h_len / 2;                                   // AS:443
+    q.h_len = c.h_len;
+    q.delta = c.delta;
+    q.sqrtD = (float)std::sqrt((double)w.D);                                                  // np.sqrt(D) -> f32
+    q.prng_seeds = c.prng_seeds;
+    q.px_state = c.px_state;
+    q.px_seeds = c.px_seeds;
+    q.px_state_out = c.px_state_out;
+    q.hbuf = (uint8_t*)(wsb + quicfl_h_off(n, dim));
+    q.scale = c.scale;
+    q.info = c.info;
+    q.D = w.D;
+    q.n = n;
+    q.force_timeout = P.force_timeout;
+    q.nrm = (const float*)(wsb + w.nrm_off);
+    int rc = UQ_OK;
+    const uint32_t* polys = nullptr;
+    if (P.side == UQ_QFL_SIDE_JUMP && (rc = qfl_jump_polys(P, false, &polys))) return rc;
+    std::optional<SideFork> fk;
+    if (P.side != UQ_QFL_SIDE_NONE) {
+        fk.emplace(st, &rc);
+        if (rc || (rc = quicfl_send_side(q, P, polys, jump, fk->side()))) return rc;
+    }
+    if ((rc = rht_norm_front(c.x, n, dim, c.signs, c.sign_row, wsb, rot, st))) return rc;     // AS:460-470
+    if (fk && (rc = fk->join())) return rc;
+    q.rot = *rot;
+    if (q.rtab) q.pre = *rot;                // in place: a coordinate's rot is loaded a round before its value is stored
+    return launch_quicfl_send(q, x_kind, P, jump, st);
+}
 
 int uq_quicfl_compress_f32(const float* x, int64_t n, int64_t dim, const int8_t* signs, const int32_t* sign_row,
                            const float* table_xp, const uint32_t* table_packed, int64_t table_numel, int32_t h_len,
@@ -404,111 +517,17 @@ int uq_quicfl_compress_f32(const float* x, int64_t n, int64_t dim, const int8_t*
                            uint32_t* px_state_out, void* X, int32_t x_kind, uint8_t* exact_mask, float* exact_vals,
                            int32_t* exact_count, float* scale, int32_t* info, void* ws, size_t ws_bytes,
                            void* stream) {
-    if (n < 0 || dim < 0) return fail(UQ_E_INVALID, "n and dim must be >= 0");
-    if (n > 65535) return fail(UQ_E_INVALID, "at most 65535 messages per call");
-    if (dim > ((int64_t)1 << 28)) return fail(UQ_E_INVALID, "dim must be <= 2^28");
-    if (h_len < 1 || h_len > 256) return fail(UQ_E_INVALID, "h_len must be 1..256");
-    if (table_numel < h_len || table_numel % h_len) return fail(UQ_E_INVALID, "table_numel must be a multiple of h_len");
-    if (table_numel >= ((int64_t)1 << 24)) return fail(UQ_E_INVALID, "table_numel must be below 2^24");
-    if (x_kind != 0 && x_kind != 1) return fail(UQ_E_INVALID, "x_kind must be 0 (int64) or 1 (uint8)");
-    if (n == 0 || dim == 0) return UQ_OK;
-    if (!x || !signs || !table_xp || !prng_seeds || !X || !exact_mask || !exact_vals || !exact_count || !scale || !info)
-        return fail(UQ_E_INVALID, "null pointer");
-    if (!px_state && !px_seeds) return fail(UQ_E_INVALID, "px_state or px_seeds is required");
-    const RhtLayout w = rht_layout(n, dim);
-    const size_t hoff = quicfl_h_off(n, dim);
-    if (!ws || ws_bytes < quicfl_ws_total(n, dim)) return fail(UQ_E_WORKSPACE, "workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    char* wsb = (char*)ws;
-    QflJumpLaunch jl;
-    int rc = quicfl_jump_fork(n, w.D, dim, prng_seeds, px_state, px_seeds, h_len, wsb, st, &jl);
-    if (rc) return rc;
-    const QflJoinGuard join_guard{jl, st};
-    float* rot = nullptr;
-    rc = rht_norm_front(x, n, dim, signs, sign_row, wsb, &rot, st);                     // AS:460-470
-    if (rc) return rc;
+    const QflSendCall c{x, n, dim, signs, sign_row, table_xp, table_packed, table_numel, h_len, delta, prng_seeds,
+                        px_state, px_seeds, px_state_out, scale, info, ws, ws_bytes, stream};
     QflSendArgs q{};
-    q.rot = rot;
-    q.nrm = (const float*)(wsb + w.nrm_off);
-    q.tab = (const float2*)table_xp;
-    q.tabp = table_packed;
-    q.numel = table_numel;
-    q.half = ((table_numel / h_len) - 1) * h_len / 2;                                        // AS:443
-    q.h_len = h_len;
-    q.delta = delta;
-    q.sqrtD = (float)std::sqrt((double)w.D);                                                  // np.sqrt(D) -> f32
-    q.prng_seeds = prng_seeds;
-    q.px_state = px_state;
-    q.px_seeds = px_seeds;
-    q.px_state_out = px_state_out;
-    q.hbuf = (uint8_t*)(wsb + hoff);
     q.X = X;
     q.x_kind = x_kind;
     q.mask = exact_mask;
     q.ev = exact_vals;
     q.ecount = exact_count;
-    q.scale = scale;
-    q.info = info;
-    q.D = w.D;
-    q.n = n;
-    return launch_quicfl_send(q, x_kind, jl, st);
-}
-
-// By batch size and the plan's cost model: the jump path (KQ0s + KQ0j + KQ1j + KQ1f: every run
-// of every message at once from jumped stream blocks) when it beats a wave per message, else up
-// to 256 the team kernel KQ1t (scouts + runs in one workgroup per message), batches a wave per
-// message (KQ1).  Test hooks: bit 1 the
-// one-wave kernel, bit 2 (or bit 0, whose timeouts only the team's runs can report) KQ1t.
-static int launch_quicfl_send(QflSendArgs& q, int32_t x_kind, const QflJumpLaunch& jl, hipStream_t st) {
-    const int hooks = g_quicfl_hooks.load();
-    q.force_timeout = hooks & 1;
-    const int64_t n = q.n;
-    const QflJumpPlan jp = qfl_jump_plan(n, q.D);
-    if (jl.use) {
-        int rc = hip_check(hipStreamWaitEvent(st, jl.sb->join, 0), "wait join");   // KQ0s + KQ0j done
-        if (rc) return rc;
-        QflRunArgs ra{};
-        ra.parts = jl.parts;
-        ra.runinfo = (int32_t*)(jl.parts + (size_t)n * jl.jp.R * 3 * kMjParts * kMtN);
-        ra.R = jl.jp.R;
-        ra.L = jl.jp.L;
-        ra.passa_done = jl.passa_runs ? 1 : 0;
-        const dim3 rgrid((unsigned)((n * jl.jp.R + kQfWavesPerWG - 1) / kQfWavesPerWG)), blk(64 * kQfWavesPerWG);
-        const bool w2 = n * jl.jp.R > kQfRunWaves1;
-#define UQ_QRUNS(XK)                                                                                        \
-    if (w2) hipLaunchKernelGGL((quicfl_send_runs_kernel<XK, true>), rgrid, blk, 0, st, q, ra);               \
-    else hipLaunchKernelGGL((quicfl_send_runs_kernel<XK, false>), rgrid, blk, 0, st, q, ra);
-        if (x_kind == 2) { UQ_QRUNS(2) } else if (x_kind == 0) { UQ_QRUNS(0) } else { UQ_QRUNS(1) }
-#undef UQ_QRUNS
-        rc = hip_check(hipGetLastError(), "quicfl_send_runs_kernel launch");
-        if (rc) return rc;
-        hipLaunchKernelGGL(quicfl_send_fin_kernel, dim3((unsigned)((n + kQfWavesPerWG - 1) / kQfWavesPerWG)), blk, 0, st,
-                           q, ra);
-        return hip_check(hipGetLastError(), "quicfl_send_fin_kernel launch");
-    }
-    if (!(hooks & 2) && ((hooks & 5) || !jp.use) && n <= kQfTeamMaxN && q.D >= (int64_t)kMtN * kQfRuns &&
-        q.D <= kQfTeamMaxD) {
-        if (x_kind == 2)
-            hipLaunchKernelGGL(quicfl_send_team_kernel<2>, dim3((unsigned)n), dim3(64 * kQfTeamWaves), 0, st, q);
-        else if (x_kind == 0)
-            hipLaunchKernelGGL(quicfl_send_team_kernel<0>, dim3((unsigned)n), dim3(64 * kQfTeamWaves), 0, st, q);
-        else
-            hipLaunchKernelGGL(quicfl_send_team_kernel<1>, dim3((unsigned)n), dim3(64 * kQfTeamWaves), 0, st, q);
-        return hip_check(hipGetLastError(), "quicfl_send_team_kernel launch");
-    }
-    const dim3 grid((unsigned)((n + kQfWavesPerWG - 1) / kQfWavesPerWG));
-    if (jl.passa) {                                  // KQ1a (pass A) ran on the side stream
-        const int rc = hip_check(hipStreamWaitEvent(st, jl.sb->join, 0), "wait join");
-        if (rc) return rc;
-        q.lstate = jl.lstate;
-    }
-    if (x_kind == 2)
-        hipLaunchKernelGGL(quicfl_send_wave_kernel<2>, grid, dim3(64 * kQfWavesPerWG), 0, st, q);
-    else if (x_kind == 0)
-        hipLaunchKernelGGL(quicfl_send_wave_kernel<0>, grid, dim3(64 * kQfWavesPerWG), 0, st, q);
-    else
-        hipLaunchKernelGGL(quicfl_send_wave_kernel<1>, grid, dim3(64 * kQfWavesPerWG), 0, st, q);
-    return hip_check(hipGetLastError(), "quicfl_send_wave_kernel launch");
+    float* rot = nullptr;
+    return quicfl_send(c, x_kind != 0 && x_kind != 1 ? "x_kind must be 0 (int64) or 1 (uint8)" : nullptr,
+                       !X || !exact_mask || !exact_vals || !exact_count || !scale, q, x_kind, &rot);
 }
 
 // QUICFL_quantize (AS:814-832) for a batch: the sender as uq_quicfl_compress_f32 with the
@@ -519,54 +538,16 @@ int uq_quicfl_quantize_f32(const float* x, int64_t n, int64_t dim, const int8_t*
                            float delta, const float* recv_table, int32_t recv_numel, const int32_t* prng_seeds,
                            const uint32_t* px_state, const int32_t* px_seeds, uint32_t* px_state_out, float* out,
                            float* scale, int32_t* info, void* ws, size_t ws_bytes, void* stream) {
-    if (n < 0 || dim < 0) return fail(UQ_E_INVALID, "n and dim must be >= 0");
-    if (n > 65535) return fail(UQ_E_INVALID, "at most 65535 messages per call");
-    if (dim > ((int64_t)1 << 28)) return fail(UQ_E_INVALID, "dim must be <= 2^28");
-    if (h_len < 1 || h_len > 256) return fail(UQ_E_INVALID, "h_len must be 1..256");
-    if (table_numel < h_len || table_numel % h_len) return fail(UQ_E_INVALID, "table_numel must be a multiple of h_len");
-    if (table_numel >= ((int64_t)1 << 24)) return fail(UQ_E_INVALID, "table_numel must be below 2^24");
-    if (recv_numel < 1 || recv_numel > kQflRecvTab) return fail(UQ_E_INVALID, "receiver table must hold 1..1024 entries");
-    if (n == 0 || dim == 0) return UQ_OK;
-    if (!x || !signs || !table_xp || !recv_table || !prng_seeds || !out || !info)
-        return fail(UQ_E_INVALID, "null pointer");
-    if (!px_state && !px_seeds) return fail(UQ_E_INVALID, "px_state or px_seeds is required");
-    const RhtLayout w = rht_layout(n, dim);
-    const size_t hoff = quicfl_h_off(n, dim);
-    if (!ws || ws_bytes < quicfl_ws_total(n, dim)) return fail(UQ_E_WORKSPACE, "workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    char* wsb = (char*)ws;
-    QflJumpLaunch jl;
-    int rc = quicfl_jump_fork(n, w.D, dim, prng_seeds, px_state, px_seeds, h_len, wsb, st, &jl);
-    if (rc) return rc;
-    const QflJoinGuard join_guard{jl, st};
-    float* rot = nullptr;
-    rc = rht_norm_front(x, n, dim, signs, sign_row, wsb, &rot, st);                     // AS:460-470
-    if (rc) return rc;
+    const QflSendCall c{x, n, dim, signs, sign_row, table_xp, table_packed, table_numel, h_len, delta, prng_seeds,
+                        px_state, px_seeds, px_state_out, scale, info, ws, ws_bytes, stream};
     QflSendArgs q{};
-    q.rot = rot;
-    q.nrm = (const float*)(wsb + w.nrm_off);
-    q.tab = (const float2*)table_xp;
-    q.tabp = table_packed;
-    q.numel = table_numel;
-    q.half = ((table_numel / h_len) - 1) * h_len / 2;                                        // AS:443
-    q.h_len = h_len;
-    q.delta = delta;
-    q.sqrtD = (float)std::sqrt((double)w.D);
-    q.prng_seeds = prng_seeds;
-    q.px_state = px_state;
-    q.px_seeds = px_seeds;
-    q.px_state_out = px_state_out;
-    q.hbuf = (uint8_t*)(wsb + hoff);
-    q.scale = scale;
-    q.info = info;
-    q.D = w.D;
-    q.n = n;
     q.rtab = recv_table;
     q.rtab_n = recv_numel;
-    q.pre = rot;                       // in place: a coordinate's rot is loaded a round before its value is stored
-    rc = launch_quicfl_send(q, 2, jl, st);              // (2: the fused instances)                 AS:455-503, 526-532
-    if (rc) return rc;
-    return rht_inverse(rot, out, n, w.D, dim, signs, sign_row, st);                           // AS:533-535
+    float* rot = nullptr;
+    const int rc = quicfl_send(c, recv_numel < 1 || recv_numel > kQflRecvTab ? "receiver table must hold 1..1024 entries" : nullptr,
+                               !recv_table || !out, q, 2, &rot);        // (2: the fused instances)  AS:455-503, 526-532
+    if (rc || !rot) return rc;
+    return rht_inverse(rot, out, n, rht_layout(n, dim).D, dim, signs, sign_row, (hipStream_t)stream);   // AS:533-535
 }
 
 // xxHash64 (the public XXH64 algorithm), for AS:457's prng seed

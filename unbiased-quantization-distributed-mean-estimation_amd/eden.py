@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .quantizer import _as_device_f32_2d, _device, _ptr, _stream_ptr, _workspace
+from .quantizer import _as_device_f32_2d, _as_device_vec, _device, _ptr, _stream_ptr, _workspace
 
 __all__ = ["EDEN_quantize_Hadamard", "eden_quantize", "eden_compress", "eden_decompress", "EdenMessage",
            "rht_signs", "padded_dim", "randomized_hadamard_transform", "randomized_inverse_hadamard_transform"]
@@ -295,10 +295,7 @@ def EDEN_quantize_Hadamard(input_vector, bits_per_dimension=1):
     seed from torch's global CPU generator like the CPU reference (AS:797) and returns a
     NumPy f32 array (AS:811)."""
     dev = _device()
-    if torch.is_tensor(input_vector):
-        v = input_vector.detach().to(device=dev, dtype=torch.float32).reshape(-1)
-    else:
-        v = torch.tensor(np.asarray(input_vector), dtype=torch.float32, device=dev).reshape(-1)
+    v = _as_device_vec(input_vector, dev)
     seed = int(torch.randint(0, _SEEDS, (1,)).item())
     out = eden_quantize(v.view(1, -1), bits_per_dimension, seeds=[seed])
     # the NumPy result comes back through pinned memory (torch's caching host allocator):

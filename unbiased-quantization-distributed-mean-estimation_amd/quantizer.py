@@ -104,6 +104,13 @@ def _as_device_f32_2d(x, dev) -> torch.Tensor:
     return x.to(device=dev, dtype=torch.float32).contiguous()
 
 
+def _as_device_vec(v, dev) -> torch.Tensor:
+    """A drop-in's input vector (tensor or array-like) as a flat f32 tensor on the device."""
+    if torch.is_tensor(v):
+        return v.detach().to(device=dev, dtype=torch.float32).reshape(-1)
+    return torch.tensor(np.asarray(v), dtype=torch.float32, device=dev).reshape(-1)
+
+
 def _resolve_m(bits, m, d):
     if m is not None:
         return int(m)

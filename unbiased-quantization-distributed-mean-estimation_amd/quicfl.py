@@ -28,13 +28,14 @@ import os
 import struct
 import threading
 from dataclasses import dataclass
+from types import SimpleNamespace
 
 import numpy as np
 import torch
 
 from . import _lib
 from .eden import _sign_rows, padded_dim, randomized_inverse_hadamard_transform
-from .quantizer import _as_device_f32_2d, _device, _ptr, _stream_ptr, _workspace
+from .quantizer import _as_device_f32_2d, _as_device_vec, _device, _ptr, _stream_ptr, _workspace
 
 __all__ = ["QuicFLReceiver", "QuicFLSender", "QuicFLMessages", "QUICFL_quantize", "quicfl_compress",
            "quicfl_decompress", "quicfl_decompress_messages", "quicfl_quantize", "prng_seed", "set_tables_prefix"]
@@ -294,6 +295,38 @@ def _raise_send_flags(flags: int) -> None:
         raise RuntimeError("uq_quicfl_compress_f32: internal wait ran out (results invalid)")
 
 
+def _send_prologue(x, nbits, seeds, rotation_seeds, sender, px_seeds, px_states, words):
+    """What quicfl_compress and quicfl_quantize do before their call: the batch on the device, the
+    seeds hashed to prng seeds (AS:457), the per-message inputs (_send_inputs), `words` zeroed
+    int32 per message (the flags first) with the end states behind them, and -- for a batch that
+    is not empty -- the C call's leading, generator and trailing arguments (sign rows, tables
+    and workspace; `keep` holds their tensors)."""
+    dev = _device()
+    dd = sender.data[nbits]
+    x = _as_device_f32_2d(x, dev)
+    n, d = x.shape
+    s = [int(v) for v in torch.as_tensor(seeds).reshape(-1).tolist()] if not isinstance(seeds, (list, tuple)) else list(seeds)
+    rs = torch.as_tensor(rotation_seeds, dtype=torch.int64).reshape(-1)
+    if len(s) != n or rs.numel() != n:
+        raise ValueError("one seed and one rotation seed per message")
+    ps = torch.tensor([prng_seed(v) for v in s], dtype=torch.int64)
+    ps_d, st_in, pxs_d, nst = _send_inputs(ps, n, px_seeds, px_states, dev)
+    dout = torch.zeros(words * n + nst, dtype=torch.int32, device=dev)
+    a = SimpleNamespace(dev=dev, x=x, n=n, d=d, D=padded_dim(d), h_len=int(dd["h_len"]), rs=rs, ps=ps, nst=nst, dout=dout,
+                        info=dout[:n], st_out=dout[words * n:].view(n, STATE_WORDS) if nst else None)
+    if n and d:
+        tab, rows = _sign_rows(rs, a.D, dev)
+        xp = sender.table_xp(nbits, dev)
+        tp = sender.table_packed(nbits, dev) if _USE_PACKED else None
+        ws = _ws(n, d, dev)
+        a.keep = (tab, rows, xp, tp, ws, ps_d, st_in, pxs_d)
+        a.head = (_ptr(x), n, d, _ptr(tab), _ptr(rows), _ptr(xp), _ptr(tp), xp.shape[0], a.h_len,
+                  float(np.float32(dd["delta"])))
+        a.gens = (_ptr(ps_d), _ptr(st_in), _ptr(pxs_d), _ptr(a.st_out))
+        a.tail = (_ptr(ws), ws.numel(), _stream_ptr(dev))
+    return a
+
+
 def quicfl_compress(x, nbits: int, seeds, rotation_seeds, *, sender: QuicFLSender, px_seeds=None, px_states=None,
                     x_dtype=torch.uint8, _state_out: bool = False):
     """QuicFLSender.compress (AS:455-503) for every row of x [n, d].  seeds: the messages'
@@ -302,43 +335,25 @@ def quicfl_compress(x, nbits: int, seeds, rotation_seeds, *, sender: QuicFLSende
     px_seeds[j], or from px_states[j] ([626] = left, next, state words of a torch CPU
     generator, see generator_words).  X is returned as uint8 (x_dtype=torch.uint8, values
     outside 0..255 raise) or int64 (the reference's X.long())."""
-    dev = _device()
-    dd = sender.data[nbits]
-    x = _as_device_f32_2d(x, dev)
-    n, d = x.shape
-    D = padded_dim(d)
-    s = [int(v) for v in torch.as_tensor(seeds).reshape(-1).tolist()] if not isinstance(seeds, (list, tuple)) else list(seeds)
-    rs = torch.as_tensor(rotation_seeds, dtype=torch.int64).reshape(-1)
-    if len(s) != n or rs.numel() != n:
-        raise ValueError("one seed and one rotation seed per message")
-    ps = torch.tensor([prng_seed(v) for v in s], dtype=torch.int64)
     if x_dtype not in (torch.uint8, torch.int64):
         raise ValueError("x_dtype must be torch.uint8 or torch.int64")
-    X = torch.empty((n, D), dtype=x_dtype, device=dev)
-    mask = torch.empty((n, D), dtype=torch.bool, device=dev)
-    ev = torch.empty((n, D), dtype=torch.float32, device=dev)
+    a = _send_prologue(x, nbits, seeds, rotation_seeds, sender, px_seeds, px_states, 2)
+    n, dev = a.n, a.dev
+    X = torch.empty((n, a.D), dtype=x_dtype, device=dev)
+    mask = torch.empty((n, a.D), dtype=torch.bool, device=dev)
+    ev = torch.empty((n, a.D), dtype=torch.float32, device=dev)
     scale = torch.empty(n, dtype=torch.float32, device=dev)
-    ps_d, st_in, pxs_d, nst = _send_inputs(ps, n, px_seeds, px_states, dev)
-    dout = torch.zeros(2 * n + nst, dtype=torch.int32, device=dev)
-    info, cnt_d = dout[:n], dout[n:2 * n]
-    st_out = dout[2 * n:].view(n, STATE_WORDS) if nst else None
-    hout = np.zeros(2 * n + nst, np.int32)
-    if n and d:
-        tab, rows = _sign_rows(rs, D, dev)
-        xp = sender.table_xp(nbits, dev)
-        tp = sender.table_packed(nbits, dev) if _USE_PACKED else None
-        ws = _ws(n, d, dev)
+    hout = np.zeros(a.dout.numel(), np.int32)
+    if n and a.d:
         _lib.check(_lib.load().uq_quicfl_compress_f32(
-            _ptr(x), n, d, _ptr(tab), _ptr(rows), _ptr(xp), _ptr(tp), xp.shape[0], int(dd["h_len"]),
-            float(np.float32(dd["delta"])), _ptr(ps_d), _ptr(st_in), _ptr(pxs_d), _ptr(st_out),
-            _ptr(X), 0 if x_dtype == torch.int64 else 1, _ptr(mask), _ptr(ev), _ptr(cnt_d), _ptr(scale), _ptr(info),
-            _ptr(ws), ws.numel(), _stream_ptr(dev)), "uq_quicfl_compress_f32")
-        hout = dout.cpu().numpy()
+            *a.head, *a.gens, _ptr(X), 0 if x_dtype == torch.int64 else 1, _ptr(mask), _ptr(ev), _ptr(a.dout[n:2 * n]),
+            _ptr(scale), _ptr(a.info), *a.tail), "uq_quicfl_compress_f32")
+        hout = a.dout.cpu().numpy()
         _raise_send_flags(int(np.bitwise_or.reduce(hout[:n])) if n else 0)
     msg = QuicFLMessages(X=X, exact_mask=mask, exact_vals=ev, exact_count=torch.from_numpy(hout[n:2 * n].copy()),
-                         scale=scale, prng_seeds=ps, rotation_seeds=rs, dim=d, nbits=nbits, h_len=int(dd["h_len"]))
+                         scale=scale, prng_seeds=a.ps, rotation_seeds=a.rs, dim=a.d, nbits=nbits, h_len=a.h_len)
     if _state_out:
-        new = hout[2 * n:].reshape(n, STATE_WORDS).view(np.uint32).copy() if nst else None
+        new = hout[2 * n:].reshape(n, STATE_WORDS).view(np.uint32).copy() if a.nst else None
         return msg, new
     return msg
 
@@ -434,6 +449,7 @@ class QuicFLReceiver:
     def __init__(self, device=None, bits=(1, 2, 3, 4), sr_bits=(6, 5, 4, 4), prefix=None, tables=None):
         self.device = device if device is not None else _device()
         self.recv_table = {}
+        self._dev_tables = {}
         if tables is not None:                      # {nbits: [rows, h_len] tensor or array}
             for b, t in tables.items():
                 self.recv_table[int(b)] = torch.as_tensor(t, dtype=torch.float32)
@@ -458,10 +474,8 @@ class QuicFLReceiver:
         """The receiver table on the device (copied once per device)."""
         dev = _device()
         key = ("_dev", int(nbits), dev.index)
-        t = self._dev_tables.get(key) if hasattr(self, "_dev_tables") else None
+        t = self._dev_tables.get(key)
         if t is None:
-            if not hasattr(self, "_dev_tables"):
-                self._dev_tables = {}
             t = self.recv_table[int(nbits)].to(dev).contiguous()
             self._dev_tables[key] = t
         return t
@@ -515,32 +529,14 @@ def quicfl_quantize(x, nbits: int, seeds, rotation_seeds, *, sender: QuicFLSende
     h is the sender's own randint stream, so it is not regenerated, and no message is written),
     then the inverse RHT.  Returns (out [n, d], end states [n, 626] or None, scale [n]).
     Raises like the sender, then like the receiver (IndexError from its take, AS:530)."""
-    dev = _device()
-    dd = sender.data[nbits]
-    x = _as_device_f32_2d(x, dev)
-    n, d = x.shape
-    D = padded_dim(d)
-    s = [int(v) for v in torch.as_tensor(seeds).reshape(-1).tolist()] if not isinstance(seeds, (list, tuple)) else list(seeds)
-    rs = torch.as_tensor(rotation_seeds, dtype=torch.int64).reshape(-1)
-    if len(s) != n or rs.numel() != n:
-        raise ValueError("one seed and one rotation seed per message")
-    ps = torch.tensor([prng_seed(v) for v in s], dtype=torch.int64)
+    a = _send_prologue(x, nbits, seeds, rotation_seeds, sender, px_seeds, px_states, 1)
+    n, d, dev, dout, nst = a.n, a.d, a.dev, a.dout, a.nst
     rt = torch.as_tensor(recv_table, dtype=torch.float32).to(dev).contiguous().reshape(-1)
-    ps_d, st_in, pxs_d, nst = _send_inputs(ps, n, px_seeds, px_states, dev)
     out = torch.empty((n, d), dtype=torch.float32, device=dev)
     scale = torch.empty(n, dtype=torch.float32, device=dev)
-    dout = torch.zeros(n + nst, dtype=torch.int32, device=dev)
-    info = dout[:n]
-    st_out = dout[n:].view(n, STATE_WORDS) if nst else None
     if n and d:
-        tab, rows = _sign_rows(rs, D, dev)
-        xp = sender.table_xp(nbits, dev)
-        tp = sender.table_packed(nbits, dev) if _USE_PACKED else None
-        ws = _ws(n, d, dev)
         _lib.check(_lib.load().uq_quicfl_quantize_f32(
-            _ptr(x), n, d, _ptr(tab), _ptr(rows), _ptr(xp), _ptr(tp), xp.shape[0], int(dd["h_len"]),
-            float(np.float32(dd["delta"])), _ptr(rt), rt.numel(), _ptr(ps_d), _ptr(st_in), _ptr(pxs_d), _ptr(st_out),
-            _ptr(out), _ptr(scale), _ptr(info), _ptr(ws), ws.numel(), _stream_ptr(dev)), "uq_quicfl_quantize_f32")
+            *a.head, _ptr(rt), rt.numel(), *a.gens, _ptr(out), _ptr(scale), _ptr(a.info), *a.tail), "uq_quicfl_quantize_f32")
     if _host_out:                          # the result and the flags / states in one synchronisation
         host = torch.empty(out.numel(), dtype=torch.float32, pin_memory=True)
         hsmall = torch.empty(dout.numel(), dtype=torch.int32, pin_memory=True)
@@ -572,10 +568,7 @@ def QUICFL_quantize(input_vector, bits_per_dimension=1):
     generator, left where the reference leaves it) and the receiver fused in one pass
     (quicfl_quantize); returns a NumPy f32 array of length d."""
     dev = _device()
-    if torch.is_tensor(input_vector):
-        v = input_vector.detach().to(device=dev, dtype=torch.float32).reshape(-1)
-    else:
-        v = torch.tensor(np.asarray(input_vector), dtype=torch.float32, device=dev).reshape(-1)
+    v = _as_device_vec(input_vector, dev)
     sender, receiver = _dropin_pair()
     seed = int(torch.randint(0, 100, (1,)).item())
     nbits = bits_per_dimension
