@@ -107,6 +107,39 @@ int uq_test_unbiased_plan(int64_t n, int64_t d, int64_t ldq, int64_t ldc, int32_
                           int32_t codes_aligned, int32_t has_out, int32_t has_codes, int32_t nib, int32_t l1_given,
                           int32_t slots, int64_t* plan_out, int32_t cap);
 int uq_test_last_unbiased_plan(int64_t* plan_out, int32_t cap);
+/* Test hooks of the biased quantizer's dispatch (uq_type_biased_f32 computes one plan from n, d,
+ * tie_policy and the alignment of x and out, and launches what it names; DESIGN.md 4.2 has the
+ * table).  A plan is UQ_BIASED_PLAN_FIELDS int64 values, of which min(cap, UQ_BIASED_PLAN_FIELDS)
+ * are written:
+ *   [0] front (UQ_BIASED_FRONT_*)   [1] tie mode (UQ_BIASED_TIES_*; for the small-checked front:
+ *   the mode the call takes when a row is ambiguous)   [2] replay form (UQ_BIASED_REPLAY_*)
+ *   KB7a's levels (0 without them): [3] levels, [4] of which before KB6 starts, [5] workgroups
+ *   per level launch   [6] S: replay slots, min(n, 256)   [7] vec4: 16-byte accesses to x and out
+ *   [8] cand_multi: the candidate digits over [9] cspans workgroups per client   [10] cap: u32 of
+ *   the candidate region per client   [11] capf = cap / 2: listed pairs per client at most
+ *   [12] output tiles per client   [13] clear_bits: the tie bits are cleared by a memset
+ *   [14] outcome, known after the host check of the small-checked front and the checked tie mode:
+ *   1 when the multi-kernel path / the replay chain ran, 0 when it was skipped; -1 in every
+ *   other mode and from uq_test_biased_plan.
+ * uq_test_biased_plan: host only, launches nothing: the plan of a call of that shape and policy
+ * (alignment as flags), with uq_type_biased_f32's own checks of n, d and tie_policy.  Front 0
+ * for n == 0 or d == 0.
+ * uq_test_last_biased_plan: the plan of this thread's last uq_type_biased_f32 call (front 0
+ * when it launched nothing). */
+#define UQ_BIASED_PLAN_FIELDS 15
+#define UQ_BIASED_FRONT_NONE 0
+#define UQ_BIASED_FRONT_SMALL 1         /* KB-small alone (lowest-index rule) */
+#define UQ_BIASED_FRONT_SMALL_CHECKED 2 /* KB-small, then the multi-kernel path if a row is ambiguous */
+#define UQ_BIASED_FRONT_FULL 3          /* the multi-kernel path */
+#define UQ_BIASED_TIES_LOWEST 0         /* lowest-index rule: no replay */
+#define UQ_BIASED_TIES_FORK 1           /* torch ties, the replay on the side stream beside KB6 */
+#define UQ_BIASED_TIES_CHECKED 2        /* torch ties, one stream, the replay skipped when no row is listed */
+#define UQ_BIASED_REPLAY_NONE 0
+#define UQ_BIASED_REPLAY_ONE_KERNEL 1
+#define UQ_BIASED_REPLAY_LEVELS 2
+int uq_test_biased_plan(int64_t n, int64_t d, int32_t tie_policy, int32_t x_aligned, int32_t out_aligned,
+                        int64_t* plan_out, int32_t cap);
+int uq_test_last_biased_plan(int64_t* plan_out, int32_t cap);
 /* Host-only, for tests and tools: the MT19937 state (ATen's 624-word array, block-aligned) that
  * `blocks` twists ahead of state624, computed the way the QUIC-FL sender's jump path does it
  * (t^(624 (blocks - 1)) mod phi, phi from Berlekamp-Massey; the correlation with the stream's

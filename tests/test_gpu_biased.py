@@ -6,6 +6,7 @@ import torch
 
 from oracle import uq_oracle_c as C
 from oracle.uq_oracle import rate_to_m
+from tests import biased_plan_hook as H
 from tests import golden_data as G
 
 pytestmark = pytest.mark.gpu
@@ -22,6 +23,12 @@ def uq(gpu_ready):
 @pytest.fixture(scope="module")
 def cases():
     return list(G.biased_vectors())
+
+
+def last_plan():
+    """The plan of the biased call this thread made last (uq_test_last_biased_plan)."""
+    from uqdme_amd._lib import load
+    return H.last_plan(load())
 
 
 def run(uq, x, R, T, ties):
@@ -349,6 +356,9 @@ def test_failed_replay_falls_back_to_index_order(uq, n, d):
     assert load().uq_test_force_replay_failure(1) == 0
     try:
         out_t, info = uq.biased_quantize(x, m=m, torch_threads=1, ties="torch", return_info=True)
+        p = last_plan()
+        assert (p["front"], p["ties"]) == (H.FULL, H.FORK), p
+        assert p["replay"] == (H.ONE_KERNEL if n == 3 else H.LEVELS), p
         torch.cuda.synchronize()
         with pytest.raises(uq.UQError):
             uq.check_status()
@@ -360,11 +370,14 @@ def test_failed_replay_falls_back_to_index_order(uq, n, d):
     uq.check_status()
 
 
-@pytest.mark.parametrize("d", [(1 << 17) + 5, 1 << 20])
+@pytest.mark.parametrize("d", [(1 << 17) + 5, (1 << 17) + 21, 1 << 20])
 def test_candidate_digits_few_and_many_clients_agree(uq, d):
     """Batches of <= 16 clients run the candidate digits (KB4d) over many workgroups per
-    client, larger ones one workgroup per client: the same rows give the same bits either
-    way (torch ties and lowest index), and both match the oracle."""
+    client where the listed pairs fill more than one span (capf = d / 16 > 8192: from
+    d = 2^17 + 16 on), larger ones one workgroup per client: the same rows give the same bits
+    either way (torch ties and lowest index), and both match the oracle.  At d = 2^17 + 5 one
+    span holds the pairs and both batches take the one-workgroup form."""
+    multi = d // 16 > 8192
     rng = np.random.default_rng(d % 977)
     x = rng.standard_normal((17, d)).astype(f32)
     x[3] = np.round(x[3] * 4) / 4                      # tie-heavy rows
@@ -373,7 +386,10 @@ def test_candidate_digits_few_and_many_clients_agree(uq, d):
     m = rate_to_m(1, d)
     for ties, code in (("torch", 0), ("lowest", 1)):
         few = uq.biased_quantize(xt[:16], m=m, torch_threads=1, ties=ties).cpu().numpy()
+        p = last_plan()
+        assert p["cand_multi"] == multi and p["cspans"] == -(-(d // 16) // 8192), p
         many = uq.biased_quantize(xt, m=m, torch_threads=1, ties=ties).cpu().numpy()
+        assert not last_plan()["cand_multi"]
         assert G.bits_equal(few, many[:16]), ties
         one = uq.biased_quantize(xt[9:10], m=m, torch_threads=1, ties=ties).cpu().numpy()
         assert G.bits_equal(one[0], many[9]), ties
@@ -393,6 +409,8 @@ def test_few_clients_2pow22_take_level_replay(uq):
     x[3] = np.round(x[3] * 8) / 8
     m = rate_to_m(1, d)
     out, info = uq.biased_quantize(torch.as_tensor(x).cuda(), m=m, torch_threads=1, ties="torch", return_info=True)
+    p = last_plan()
+    assert (p["ties"], p["replay"], p["levels"]) == (H.FORK, H.LEVELS, 11), p
     out, info = out.cpu().numpy(), info.cpu().numpy()
     assert (info[:, 1] & 8).any(), info
     for j in range(n):
@@ -405,16 +423,22 @@ def test_few_clients_2pow22_take_level_replay(uq):
 def test_host_check_skips_replay_with_same_bits(uq, d):
     """UQ_TIES_HOST_CHECK (the per-vector drop-in's policy): when no row needs the torch-tie
     replay its kernels are skipped; when some do, they run.  Same bits as the plain call either
-    way, for tie-free and tie-heavy rows, one row and a few."""
+    way, for tie-free and tie-heavy rows, one row and a few.  (The oracle finds no threshold tie
+    in these seeds' Gaussian rows and one in every integer-valued row.)"""
     rng = np.random.default_rng(d % 1013)
     smooth = rng.standard_normal((3, d)).astype(f32)
     ties = rng.integers(-3, 4, (3, d)).astype(f32)
     m = rate_to_m(1, d)
-    for x in (smooth, ties, np.stack([smooth[0], ties[1]])):
+    for x, ran in ((smooth, (0, 0)), (ties, (1, 1)), (np.stack([smooth[0], ties[1]]), (0, 1))):
         xt = torch.as_tensor(x).cuda()
-        for rows in (xt[:1], xt):
+        for rows, want in zip((xt[:1], xt), ran):
             a, ia = uq.biased_quantize(rows, m=m, torch_threads=1, ties="torch", return_info=True)
+            p = last_plan()
+            assert (p["ties"], p["replay"], p["ran"]) == (H.FORK, H.LEVELS, -1), p
             b, ib = uq.biased_quantize(rows, m=m, torch_threads=1, ties="torch", return_info=True, host_check=True)
+            p = last_plan()
+            assert (p["front"], p["ties"], p["replay"], p["levels"]) == (H.FULL, H.CHECKED, H.LEVELS, 11), p
+            assert p["ran"] == want, (p, want)              # the replay chain: skipped for tie-free rows, run for the others
             assert torch.equal(a.view(torch.int32), b.view(torch.int32)) and torch.equal(ia, ib)
     out = uq.Type_biased_quantize(torch.as_tensor(ties[2]).cuda(), 1)
     ref = uq.biased_quantize(torch.as_tensor(ties[2:3]).cuda(), m=rate_to_m(1, d), ties="torch")
@@ -436,7 +460,22 @@ def test_small_vector_single_launch(uq, d):
     for R in (1, 4):
         m = rate_to_m(R, d)
         lo, ilo = uq.biased_quantize(xt, m=m, torch_threads=1, ties="lowest", return_info=True)
+        p = last_plan()
+        assert (p["front"], p["ran"]) == (H.SMALL, -1), p
         to, ito = uq.biased_quantize(xt, m=m, torch_threads=1, ties="torch", return_info=True, host_check=True)
+        assert last_plan()["front"] == H.SMALL_CHECKED
+        # the multi-kernel path runs exactly when the oracle finds a threshold tie in a row of the
+        # call: checked per row, smooth (row 0) and integer-valued (row 1)
+        for j in (0, 1):
+            try:
+                with np.errstate(all="ignore"):
+                    amb = bool(C.biased_quantize(x[j], m, 1, 0)[3])
+            except (RuntimeError, ValueError):             # the reference raises (AS:656 / AS:660)
+                continue
+            one = uq.biased_quantize(xt[j:j + 1], m=m, torch_threads=1, ties="torch", host_check=True)
+            p = last_plan()
+            assert (p["front"], p["ran"]) == (H.SMALL_CHECKED, int(amb)), (d, R, j, p)
+            assert torch.equal(one[0].view(torch.int32), to[j].view(torch.int32)), (d, R, j)
         for j in range(x.shape[0]):
             for rule, got, info in ((1, lo, ilo), (0, to, ito)):
                 try:
@@ -447,4 +486,29 @@ def test_small_vector_single_launch(uq, d):
                     continue
                 assert int(info[j, 0]) == D and bool(int(info[j, 1]) & 1) == A, (d, R, j, rule)
                 assert G.bits_equal(got[j].cpu().numpy(), exp), (d, R, j, rule)
+    uq.check_status()
+
+
+def test_small_checked_falls_through_to_checked_levels(uq):
+    """32 integer-valued rows of d = 8193 under the host check: KB-small finds ambiguous rows and
+    the call goes on to the multi-kernel path with the checked level chain (32 <= n <= 64 and
+    8192 < d <= 32767 is the only range where the small-checked front meets KB7a).  Same bits as
+    the plain torch-tie call (the fork, same levels), two rows against the oracle."""
+    rng = np.random.default_rng(8193)
+    n, d = 32, 8193
+    x = rng.integers(-3, 4, (n, d)).astype(f32)
+    xt = torch.as_tensor(x).cuda()
+    m = rate_to_m(1, d)
+    a, ia = uq.biased_quantize(xt, m=m, torch_threads=1, ties="torch", return_info=True)
+    p = last_plan()
+    assert (p["front"], p["ties"], p["replay"], p["levels"], p["ran"]) == (H.FULL, H.FORK, H.LEVELS, 3, -1), p
+    b, ib = uq.biased_quantize(xt, m=m, torch_threads=1, ties="torch", return_info=True, host_check=True)
+    p = last_plan()
+    assert (p["front"], p["ties"], p["replay"], p["levels"], p["ran"]) == (H.SMALL_CHECKED, H.CHECKED, H.LEVELS, 3, 1), p
+    assert torch.equal(a.view(torch.int32), b.view(torch.int32)) and torch.equal(ia, ib)
+    out = b.cpu().numpy()
+    for j in (0, 31):
+        exp, _, D, A = C.biased_quantize(x[j], m, 1, 0)
+        assert A and int(ib[j, 0]) == D, j
+        assert G.bits_equal(out[j], exp), (j, G.n_mismatch(out[j], exp))
     uq.check_status()

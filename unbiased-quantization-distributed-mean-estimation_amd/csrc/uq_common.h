@@ -551,9 +551,14 @@ l1_finalize_kernel(const float* __restrict__ x, int64_t d, L1Plan plan,
     }
 }
 
-// Launches K1a + K1b with Op.  A histogram op (Op::kHist, KB2 of the biased quantizer) takes up
-// to hist_groups_per_wg() level-1 groups per workgroup, fewer while that would leave fewer than
-// ~4096 workgroups (a few-client call keeps one group each).
+// KB2 (the k' sum with the fine-bin histogram): at most this many level-1 groups per
+// workgroup, fewer while that would leave fewer than ~4096 workgroups (a few-client call keeps
+// one group each).  1024 x 2^20: KB2 1.16 -> 0.97 ms at 4 (torch-tie batch 5.43 -> 5.21 ms,
+// lowest-index 4.23 -> 3.97 ms on one box; 8: 5.21 / 3.96), profiles/r5n_biased_gpw.jsonl.
+constexpr int kHistGroupsPerWG = 8;
+
+// Launches K1a + K1b with Op; a histogram op (Op::kHist, KB2 of the biased quantizer) with
+// kHistGroupsPerWG.
 template <class Op>
 int launch_cascade(const float* x, int64_t n, int64_t d, const L1Plan& plan, float* part, float* sum_out,
                    const float* l1, float fm, hipStream_t st, uint32_t* hist = nullptr, uint32_t* zn = nullptr) {
@@ -562,7 +567,7 @@ int launch_cascade(const float* x, int64_t n, int64_t d, const L1Plan& plan, flo
         vec4 = vec4 && (plan.nchunks == 1 || plan.cs % 4 == 0);
         int maxstep = std::max(16, 1 << plan.last.lp);
         if (plan.nchunks > 1) maxstep = std::max(maxstep, 1 << plan.full.lp);
-        const int gpw = Op::kHist ? (int)std::max<int64_t>(1, std::min<int64_t>(hist_groups_per_wg(),
+        const int gpw = Op::kHist ? (int)std::max<int64_t>(1, std::min<int64_t>(kHistGroupsPerWG,
                                                                                 (int64_t)plan.total_groups * n / 4096))
                                   : 1;
         dim3 grid((unsigned)((plan.total_groups + gpw - 1) / gpw), (unsigned)n);
@@ -585,7 +590,7 @@ int launch_cascade(const float* x, int64_t n, int64_t d, const L1Plan& plan, flo
         int rc = hip_check(hipGetLastError(), "l1_partial_kernel launch");
         if (rc) return rc;
     }
-    if (plan.nchunks == 1 && n <= 128 && plan.last.size >= 8 && plan.last.ng1 >= 64 && !std::getenv("UQDME_K1B_NARROW")) {
+    if (plan.nchunks == 1 && n <= 128 && plan.last.size >= 8 && plan.last.ng1 >= 64) {
         hipLaunchKernelGGL((l1_finalize_kernel<Op, kFinWaves, true>), dim3((unsigned)n), dim3(64 * kFinWaves),
                            (size_t)plan.nbuf * sizeof(float), st, x, d, plan, part, sum_out, l1, fm, hist, zn);
         return hip_check(hipGetLastError(), "l1_finalize_kernel (wide) launch");

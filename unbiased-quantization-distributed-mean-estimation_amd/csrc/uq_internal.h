@@ -3,7 +3,7 @@
 // Each scheme is one .hip (uq_unbiased.hip, uq_biased.hip, uq_eden.hip, uq_quicfl.hip,
 // uq_codec.hip) beside the host core, uq_core.hip.  What they share on the host is declared
 // here and defined in exactly one of them, so every piece of state (the error string, the side
-// streams, the environment knobs) exists once in the library.  Nothing here is exported: the
+// streams) exists once in the library.  Nothing here is exported: the
 // namespace has hidden visibility.  Signatures use plain types only: the kernels' argument
 // structs live in anonymous namespaces (their names are part of the kernels' symbols), so they
 // cannot cross.
@@ -15,6 +15,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <string>
+#include <type_traits>
 
 #include "../../include/uq_dme.h"
 
@@ -30,6 +31,11 @@ constexpr size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 int fail(int code, const std::string& msg);
 int hip_check(hipError_t e, const char* what);
 bool aligned16(const void* p);
+// After a kernel launch: hip_check of the launch's error.
+inline int launched(const char* what) { return hip_check(hipGetLastError(), what); }
+// A run-time flag as a compile-time constant, for the selectors of template instances.
+template <bool B>
+using Flag = std::integral_constant<bool, B>;
 
 // A second stream per device and thread (plus fork / join events) for work that can run
 // beside the caller's stream inside one call; joined back before the call returns.
@@ -42,16 +48,45 @@ struct SideStream {
 constexpr int64_t kSmallCheckMaxN = 64;    // clients per host-checked small-vector biased call
 int side_stream(SideStream** out);
 
+// Forks the thread's side stream from st; join() records the side stream's end and makes st
+// wait for it.  The destructor joins if that has not happened, so once forked the caller's
+// stream waits on every exit path: the side kernels write into the caller's workspace, which
+// may be freed or reused after an early error return.
+class SideFork {
+public:
+    SideFork(hipStream_t st, int* rc) : st_(st) {
+        if ((*rc = side_stream(&sb_))) return;
+        if ((*rc = hip_check(hipEventRecord(sb_->fork, st), "record fork"))) return;
+        if ((*rc = hip_check(hipStreamWaitEvent(sb_->s, sb_->fork, 0), "wait fork"))) return;
+        open_ = true;
+    }
+    SideFork(const SideFork&) = delete;
+    SideFork& operator=(const SideFork&) = delete;
+    ~SideFork() { (void)join(); }
+    hipStream_t side() const { return sb_->s; }
+    // The reverse wait, before the join: st waits for what the side stream holds so far.
+    int wait_mid() {
+        const int rc = hip_check(hipEventRecord(sb_->mid, sb_->s), "record mid");
+        return rc ? rc : hip_check(hipStreamWaitEvent(st_, sb_->mid, 0), "wait mid");
+    }
+    int join() {
+        if (!open_) return UQ_OK;
+        open_ = false;
+        const int rc = hip_check(hipEventRecord(sb_->join, sb_->s), "record join");
+        return rc ? rc : hip_check(hipStreamWaitEvent(st_, sb_->join, 0), "wait join");
+    }
+
+private:
+    hipStream_t st_;
+    SideStream* sb_ = nullptr;
+    bool open_ = false;
+};
+
 // ---- uq_unbiased.hip -----------------------------------------------------------------
 // AS:624 |x|.sum() of n rows in torch CPU order for T intra-op threads (K1a + K1b with AbsOp).
 // part: n * total_groups * 32 floats of the plan make_plan(d, T) gives; the caller has checked
 // that the plan exists.
 int launch_l1(const float* x, int64_t n, int64_t d, int32_t T, float* part, float* l1_out, hipStream_t st);
-
-// ---- uq_biased.hip -------------------------------------------------------------------
-// KB2's cap on level-1 groups per workgroup (env UQDME_HIST_GPW), read by launch_cascade for
-// the histogram op only.
-int hist_groups_per_wg();
 
 // ---- uq_eden.hip: the RHT and the norm as QUIC-FL's sender uses them -------------------
 // The EDEN workspace layout of (n, dim): D = dim padded to a power of two, the norms at

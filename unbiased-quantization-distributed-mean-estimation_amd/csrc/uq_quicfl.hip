@@ -125,8 +125,6 @@ int export_plan(const QflPlan& p, int64_t* out, int32_t cap) {
 // another order moves the padding between kernels, and with it tools/kernel_table.py's hashes.)
 template <int K>
 using Xk = std::integral_constant<int, K>;
-template <bool B>
-using Flag = std::integral_constant<bool, B>;
 
 template <class F>
 void select_xk(int32_t x_kind, F&& f) {
@@ -142,37 +140,6 @@ void select_xk_w2(int32_t x_kind, bool w2, F&& f) {
 
 const dim3 kWaveBlock(64 * kQfWavesPerWG), kTeamBlock(64 * kQfTeamWaves);
 dim3 wave_grid(int64_t waves) { return dim3((unsigned)((waves + kQfWavesPerWG - 1) / kQfWavesPerWG)); }
-int launched(const char* what) { return hip_check(hipGetLastError(), what); }
-
-// ---- side stream -----------------------------------------------------------------------
-// Forks the thread's side stream from st; join() records the side stream's end and makes st
-// wait for it.  The destructor joins if that has not happened, so once forked the caller's
-// stream waits on every exit path: the side kernels write into the caller's workspace, which
-// may be freed or reused after an early error return.
-class SideFork {
-public:
-    SideFork(hipStream_t st, int* rc) : st_(st) {
-        if ((*rc = side_stream(&sb_))) return;
-        if ((*rc = hip_check(hipEventRecord(sb_->fork, st), "record fork"))) return;
-        if ((*rc = hip_check(hipStreamWaitEvent(sb_->s, sb_->fork, 0), "wait fork"))) return;
-        open_ = true;
-    }
-    SideFork(const SideFork&) = delete;
-    SideFork& operator=(const SideFork&) = delete;
-    ~SideFork() { (void)join(); }
-    hipStream_t side() const { return sb_->s; }
-    int join() {
-        if (!open_) return UQ_OK;
-        open_ = false;
-        const int rc = hip_check(hipEventRecord(sb_->join, sb_->s), "record join");
-        return rc ? rc : hip_check(hipStreamWaitEvent(st_, sb_->join, 0), "wait join");
-    }
-
-private:
-    hipStream_t st_;
-    SideStream* sb_ = nullptr;
-    bool open_ = false;
-};
 
 }  // namespace
 
