@@ -140,6 +140,49 @@ int uq_test_last_unbiased_plan(int64_t* plan_out, int32_t cap);
 int uq_test_biased_plan(int64_t n, int64_t d, int32_t tie_policy, int32_t x_aligned, int32_t out_aligned,
                         int64_t* plan_out, int32_t cap);
 int uq_test_last_biased_plan(int64_t* plan_out, int32_t cap);
+/* Test hooks of the EDEN / RHT dispatch (every uq_eden_* and uq_rht_f32 call, and QUIC-FL's RHT
+ * front and inverse, computes one plan per op and launches what it names; DESIGN.md 4.3 has the
+ * table).  A plan is UQ_EDEN_PLAN_FIELDS int64 values, of which min(cap, UQ_EDEN_PLAN_FIELDS) are
+ * written:
+ *   [0] D: dim padded to a power of two (the norm op: dim itself)   [1] p: D <= 2^p
+ *   [2] norm form (UQ_EDEN_NORM_*)   [3] dot form (UQ_EDEN_DOT_*)   [4] bits of the first FWHT pass
+ *   [5] FWHT passes, then for each of UQ_EDEN_MAX_PASSES passes (0 past [5]): [6 + 4 i] lo, its
+ *   lowest index bit   [7 + 4 i] k, its bits   [8 + 4 i] kernel (UQ_EDEN_PASS_*)   [9 + 4 i]
+ *   workgroups per client (grid x; grid y is n)
+ *   [22] the forward RHT copies its result from the workspace into out   [23] tables per client
+ *   of the segmented norm (0 where the shape has no segmented region)
+ * uq_test_eden_plan: host only, launches nothing: the plan of op (UQ_EDEN_OP_*) for n clients of
+ * dim coordinates; nbits matters to compress (1 or 2), mode (uq_eden_norm_f32's) to the norm op,
+ * whose norm form is 0 when mode 2 is asked for a shape the segmented norm does not take.  No
+ * forms and no passes for n == 0 or dim == 0.
+ * uq_test_last_eden_plan: the plan of this thread's last call of that op (no passes and no forms
+ * when it launched nothing); a uq_eden_f32 call records a compress and a decompress plan. */
+#define UQ_EDEN_PLAN_FIELDS 24
+#define UQ_EDEN_MAX_PASSES 4            /* three up to D = 2^28 (12 + 8 + 8), the quantizers' limit */
+#define UQ_EDEN_OP_COMPRESS 0
+#define UQ_EDEN_OP_DECOMPRESS 1
+#define UQ_EDEN_OP_RHT_FORWARD 2
+#define UQ_EDEN_OP_RHT_INVERSE 3        /* uq_rht_f32's inverse: first pass 12 bits whatever D */
+#define UQ_EDEN_OP_NORM 4
+#define UQ_EDEN_OP_QFL_FRONT 5          /* QUIC-FL's sender: RHT + norm */
+#define UQ_EDEN_OP_QFL_INVERSE 6        /* uq_quicfl_quantize_f32's inverse RHT */
+#define UQ_EDEN_OPS 7
+#define UQ_EDEN_NORM_NONE 0
+#define UQ_EDEN_NORM_CHAINS_WHOLE 1     /* KE2, D a multiple of its 2048-float chunk */
+#define UQ_EDEN_NORM_CHAINS_GENERIC 2   /* KE2, any D */
+#define UQ_EDEN_NORM_SEGMENTED 3        /* KE2a-KE2d */
+#define UQ_EDEN_NORM_FUSED 4            /* KE2+4: norm, bins and dot in one read */
+#define UQ_EDEN_DOT_NONE 0
+#define UQ_EDEN_DOT_ONE_WAVE 1          /* KE4 */
+#define UQ_EDEN_DOT_SEGMENTED 2         /* KE4s */
+#define UQ_EDEN_DOT_FUSED_REDO 3        /* KE2+4, then KE4 for the clients it flags */
+#define UQ_EDEN_PASS_LOW16K 1
+#define UQ_EDEN_PASS_LOW4096 2
+#define UQ_EDEN_PASS_HIGH256 3
+#define UQ_EDEN_PASS_SMALL 4
+#define UQ_EDEN_PASS_GENERIC 5
+int uq_test_eden_plan(int32_t op, int64_t n, int64_t dim, int32_t nbits, int32_t mode, int64_t* plan_out, int32_t cap);
+int uq_test_last_eden_plan(int32_t op, int64_t* plan_out, int32_t cap);
 /* Host-only, for tests and tools: the MT19937 state (ATen's 624-word array, block-aligned) that
  * `blocks` twists ahead of state624, computed the way the QUIC-FL sender's jump path does it
  * (t^(624 (blocks - 1)) mod phi, phi from Berlekamp-Massey; the correlation with the stream's

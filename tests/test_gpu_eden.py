@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from oracle import uq_eden as E
+from tests import eden_plan_hook as H
 from tests import golden_data as G
 
 pytestmark = pytest.mark.gpu
@@ -25,6 +26,12 @@ def uq(gpu_ready):
 @pytest.fixture(scope="module")
 def fx():
     return G.eden()
+
+
+def last(op):
+    """The plan of this thread's last call of that op (tests/eden_plan_hook.py)."""
+    from uqdme_amd._lib import load
+    return H.last_plan(load(), op)
 
 
 def test_rht_signs_known_answers(uq, fx):
@@ -100,13 +107,17 @@ def test_rht_forward_inverse_vs_reference(uq, fx):
 
 
 def test_eden_c4_size_2pow22_vs_oracle(uq):
-    """d = 2^22 (three FWHT passes: 12 + 8 + 2 bits) and a padded d = 2^22 - 3."""
+    """d = 2^22 (two FWHT passes each way: 14 + 8 bits; one row: the segmented norm and dot) and
+    a padded d = 2^22 - 3."""
     rng = np.random.default_rng(9)
     for d in (1 << 22, (1 << 22) - 3):
         x = rng.standard_normal(d).astype(np.float32)
         for nbits in (1, 2):
             out, scale = uq.eden_quantize(torch.as_tensor(x).cuda().view(1, -1), nbits, seeds=[37],
                                           return_scale=True)
+            pc, pd = last(H.COMPRESS), last(H.DECOMPRESS)
+            assert H.kernels(pc) == H.kernels(pd) == [H.LOW16K, H.HIGH256] and H.bits(pc) == H.bits(pd) == [14, 8]
+            assert (pc["norm"], pc["dot"], pc["seg_tab_cap"]) == (H.SEG_NORM, H.SEG_DOT, 256)
             bins, sc, _, _ = E.eden_compress(x, nbits, 37)
             assert same_f32(scale.cpu()[0], sc), (d, nbits)
             exp = E.eden_decompress(bins, sc, nbits, 37, d)
@@ -130,6 +141,9 @@ def test_round_trip_fused_path_matches_compress_decompress(uq):
         sep = uq.eden_decompress(msg).cpu().numpy()
         fused = uq.eden_quantize(xt, nbits, seeds=seeds).cpu().numpy()
         assert G.bits_equal(sep, fused), nbits
+        pc, pd = last(H.COMPRESS), last(H.DECOMPRESS)            # 7 rows of 2^15: 12 + 3 bits, segmented norm and dot
+        assert H.bits(pc) == H.bits(pd) == [12, 3] and H.kernels(pc) == H.kernels(pd) == [H.LOW4096, H.GENERIC]
+        assert (pc["norm"], pc["dot"]) == (H.SEG_NORM, H.SEG_DOT)
         for j in range(len(seeds)):
             with np.errstate(invalid="ignore"):
                 bins, sc, _, _ = E.eden_compress(x[j], nbits, seeds[j])
@@ -138,13 +152,16 @@ def test_round_trip_fused_path_matches_compress_decompress(uq):
         assert np.isnan(fused[-1]).all()                        # 0 / 0 norm, as the reference
 
 
-@pytest.mark.parametrize("d", [1 << 20, (1 << 22) - 5])
+@pytest.mark.parametrize("d", [1 << 20, (1 << 21) - 5, (1 << 22) - 5])
 def test_rht_forward_two_and_three_passes_vs_oracle(uq, d):
-    """The forward RHT writes its last pass straight into the output (two passes) or copies
-    from the workspace (three passes)."""
+    """The forward RHT writes its last pass straight into the output (two passes: D = 2^20 as
+    12 + 8 bits, D = 2^22 as 14 + 8) or copies from the workspace (three passes: D = 2^21)."""
     rng = np.random.default_rng(d % 1000)
     x = rng.standard_normal(d).astype(np.float32)
     fwd = uq.randomized_hadamard_transform(torch.as_tensor(x).cuda().view(1, -1), [21]).cpu().numpy()[0]
+    p = last(H.RHT_FORWARD)
+    bits = {1 << 20: [12, 8], (1 << 21) - 5: [12, 8, 1], (1 << 22) - 5: [14, 8]}[d]
+    assert H.bits(p) == bits and p["copy_back"] == (len(bits) == 3), p
     assert G.bits_equal(fwd, E.rht(x, 21))
 
 
@@ -159,6 +176,9 @@ def test_rht_inverse_pass_counts_vs_oracle(uq, p):
     v = np.random.default_rng(p).standard_normal((2, D)).astype(np.float32)
     inv = uq.randomized_inverse_hadamard_transform(torch.as_tensor(v).cuda(), seeds).cpu().numpy()
     assert inv.shape == (2, D)
+    pl = last(H.RHT_INVERSE)
+    assert H.bits(pl) == {12: [12], 13: [12, 1], 20: [12, 8], 21: [12, 8, 1], 22: [12, 8, 2]}[p], pl
+    assert H.kernels(pl) == [H.LOW4096, H.GENERIC if p == 13 else H.HIGH256, H.SMALL][:len(pl["passes"])], pl
     for j, seed in enumerate(seeds):
         assert G.bits_equal(inv[j], E.inverse_rht(v[j], seed)), (p, j)
 
@@ -166,16 +186,29 @@ def test_rht_inverse_pass_counts_vs_oracle(uq, p):
 @pytest.mark.parametrize("d", [1, 2, 3, 5, 16, 100, 4095, 4096, 4097, 5000, 8192, 12289])
 def test_eden_dims_across_pass_shapes_vs_oracle(uq, d):
     """Dimensions around the pass shapes: a single generic pass (D < 4096), the low pass
-    alone (D = 4096, compress + decompress), two and three passes with the fused round
-    trip (D > 4096); bins / scale / outputs against the oracle, and the round trip equal to
-    compress -> decompress."""
+    alone (D = 4096, compress + decompress), two passes (D = 8192: 12 + 1, D = 16384: 12 + 2,
+    the second generic at three rows); bins / scale / outputs against the oracle, and the
+    round trip equal to compress -> decompress.  Three rows: the one-wave dot below D = 2^14
+    (1 bit fused with the norm where D is a multiple of 2048), the segmented norm and dot from
+    there."""
     rng = np.random.default_rng(d)
     n = 3
+    D = 1 if d <= 1 else 1 << (d - 1).bit_length()
+    want_bits = [D.bit_length() - 1] if D <= 4096 else [12, D.bit_length() - 13]
+    want_kernels = [H.LOW4096 if D >= 4096 else H.GENERIC] + [H.GENERIC] * (D > 4096)
     x = rng.standard_normal((n, d)).astype(np.float32)
     seeds = [int(s) for s in rng.integers(0, 100, n)]
     for nbits in (1, 2):
         xt = torch.as_tensor(x).cuda()
         out, scale = uq.eden_quantize(xt, nbits, seeds=seeds, return_scale=True)
+        pc, pd = last(H.COMPRESS), last(H.DECOMPRESS)
+        assert H.bits(pc) == H.bits(pd) == want_bits and H.kernels(pc) == H.kernels(pd) == want_kernels, (pc, pd)
+        if D >= 1 << 14:
+            assert (pc["norm"], pc["dot"]) == (H.SEG_NORM, H.SEG_DOT)
+        elif nbits == 1 and D % 2048 == 0:
+            assert (pc["norm"], pc["dot"]) == (H.FUSED_NORM, H.FUSED_REDO)
+        else:
+            assert (pc["norm"], pc["dot"]) == (H.CHAINS_WHOLE if D % 2048 == 0 else H.CHAINS_GENERIC, H.ONE_WAVE)
         msg = uq.eden_compress(xt, nbits, seeds=seeds)
         assert G.bits_equal(uq.eden_decompress(msg).cpu().numpy(), out.cpu().numpy())
         out, scale = out.cpu().numpy(), scale.cpu().numpy()
@@ -223,18 +256,23 @@ def test_scale_dot_order_adversarial(uq, n):
 
 @pytest.mark.parametrize("kind", ["wide", "smallint", "tiny"])
 def test_scale_dot_segmented_and_one_wave_agree(uq, kind):
-    """The dot's two forms (KE4s segments for <= kDotSegMaxN clients, one wave per client
-    otherwise) on the same rows: identical bins and scales, both equal to the C oracle's
-    MKL-order dot, at D = 2^14 .. 2^22 (ties, binade crossings, underflowing quotients)."""
+    """The dot's two forms (KE4s segments for <= kDotSegMaxN = 128 clients, one wave per client
+    otherwise; 130 rows keep the segmented norm) on the same rows: identical bins and scales,
+    both equal to the C oracle's MKL-order dot, at D = 2^14 .. 2^22 (ties, binade crossings,
+    underflowing quotients)."""
     from oracle import uq_oracle_c as C
     rng = np.random.default_rng(hash(kind) % 1000)
     for D in (1 << 14, 1 << 17, 1 << 20, 1 << 22):
         x = _adv_rows(rng, kind, 2, D)
         seeds = [int(s) for s in rng.integers(0, 100, 2)]
         for nbits in (1, 2):
-            few = uq.eden_compress(torch.as_tensor(x).cuda(), nbits, seeds=seeds)            # segmented
-            many = uq.eden_compress(torch.as_tensor(np.concatenate([x] * 40)).cuda(), nbits,   # one wave each
-                                    seeds=seeds * 40)
+            xt = torch.as_tensor(x).cuda()
+            few = uq.eden_compress(xt, nbits, seeds=seeds)
+            pf = last(H.COMPRESS)
+            assert (pf["norm"], pf["dot"]) == (H.SEG_NORM, H.SEG_DOT), pf
+            many = uq.eden_compress(xt.repeat(65, 1), nbits, seeds=seeds * 65)
+            pm = last(H.COMPRESS)
+            assert (pm["norm"], pm["dot"]) == (H.SEG_NORM, H.ONE_WAVE), pm
             assert torch.equal(few.bins, many.bins[:2]), (D, nbits)
             a, b = few.scale.cpu().numpy(), many.scale.cpu().numpy()[:2]
             for j in range(2):
@@ -263,6 +301,8 @@ def test_one_bit_batch_fused_norm_dot_and_its_redo(uq):
     x[12, 100] = np.nan
     seeds = [int(s) for s in rng.integers(0, 100, n)]
     msg = uq.eden_compress(torch.as_tensor(x).cuda(), 1, seeds=seeds)
+    pc = last(H.COMPRESS)
+    assert (pc["norm"], pc["dot"]) == (H.FUSED_NORM, H.FUSED_REDO), pc
     bins, sc = msg.bins.cpu().numpy(), msg.scale.cpu().numpy()
     for j in [0, 1, 3, 10, 11, 12, 150, 299]:
         with np.errstate(all="ignore"):
@@ -315,3 +355,30 @@ def test_sign_bits_equal_int8_rows(uq, d):
     if d <= 1 << 20:
         out = uq.eden_quantize(xt[:1], 1, seeds=[17]).cpu().numpy()[0]
         assert G.bits_equal(out, E.eden_quantize(x[0], 1, 17))
+
+
+@pytest.mark.parametrize("n,d,nbits,norm,rows", [
+    (129, 1 << 14, 1, H.SEG_NORM, (0, 64, 128)),            # one client past the segmented dot's 128
+    (129, 1 << 14, 2, H.SEG_NORM, (0, 64, 128)),
+    (257, 1 << 14, 2, H.CHAINS_WHOLE, (0, 128, 256)),       # one client past the segmented norm's 256, not fused: 2 bits
+    (257, 1024, 1, H.CHAINS_GENERIC, (0, 128, 256)),        # ... and not fused: D is no multiple of 2048
+])
+def test_one_wave_dot_behind_each_norm_form_vs_oracle(uq, n, d, nbits, norm, rows):
+    """The one-wave dot (KE4) after the segmented norm, the whole-chunk chains and the generic
+    chains, each at the smallest batch that takes the pair: bins, scale and output of three rows
+    against the oracle, bit for bit."""
+    rng = np.random.default_rng(n + d + nbits)
+    x = rng.standard_normal((n, d)).astype(np.float32)
+    seeds = [int(s) for s in rng.integers(0, 100, n)]
+    xt = torch.as_tensor(x).cuda()
+    msg = uq.eden_compress(xt, nbits, seeds=seeds)
+    pc = last(H.COMPRESS)
+    assert (pc["norm"], pc["dot"]) == (norm, H.ONE_WAVE), pc
+    out = uq.eden_quantize(xt, nbits, seeds=seeds)
+    assert (last(H.COMPRESS)["norm"], last(H.COMPRESS)["dot"]) == (norm, H.ONE_WAVE)
+    bins, sc, out = msg.bins.cpu().numpy(), msg.scale.cpu().numpy(), out.cpu().numpy()
+    for j in rows:
+        eb, es, _, _ = E.eden_compress(x[j], nbits, seeds[j])
+        assert np.array_equal(bins[j], eb), j
+        assert same_f32(sc[j], es), (j, sc[j], es)
+        assert G.bits_equal(out[j], E.eden_decompress(eb, es, nbits, seeds[j], d)), j

@@ -79,17 +79,22 @@ def test_segmented_norm_max_batch(lib):
 
 
 def test_drop_in_uses_segmented_norm_and_matches_batch(lib):
-    """The per-call drop-in (n = 1, segmented norm) and a 1024-row batch (sequential
-    chains) give the same EDEN output bits for the same row and seed."""
+    """The per-call drop-in (n = 1: segmented norm and dot) and a 1024-row 1-bit batch (the
+    norm fused with the bins and the dot, KE2+4) give the same EDEN output bits for the same
+    row and seed."""
     import uqdme
+    from tests import eden_plan_hook as H
+    last = lambda: H.last_plan(lib.load(), H.COMPRESS)
     rng = np.random.default_rng(4)
     d = 300000                                              # D = 2^19, zero-padded
     x = rng.standard_normal((1024, d)).astype(np.float32)
     seeds = [int(s) for s in rng.integers(0, 100, 1024)]
     xt = torch.from_numpy(x).cuda()
     batch = uqdme.eden_quantize(xt, 1, seeds=seeds)
+    assert (last()["norm"], last()["dot"]) == (H.FUSED_NORM, H.FUSED_REDO)
     for j in (0, 511, 1023):
         one = uqdme.eden_quantize(xt[j:j + 1], 1, seeds=[seeds[j]])
+        assert (last()["norm"], last()["dot"]) == (H.SEG_NORM, H.SEG_DOT)
         assert torch.equal(one[0].view(torch.int32), batch[j].view(torch.int32)), j
 
 

@@ -16,6 +16,7 @@ import torch
 pytestmark = pytest.mark.gpu
 HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 sys.path.insert(0, HERE)
+from tests import eden_plan_hook as EH  # noqa: E402
 from tests import quicfl_plan_hook as H  # noqa: E402
 from quicfl_tables import DATA, SR_BITS, data_txt, sender_tables  # noqa: E402
 
@@ -99,6 +100,11 @@ def test_dropin_2pow22_vs_reference(fx, tmp_path):
             x = gen(c["kind"], c["vseed"], c["dim"])
             torch.manual_seed(c["gseed"])
             out = uqdme.QUICFL_quantize(x, c["nbits"])
+            if c["dim"] > 1 << 21:                          # D = 2^22: 14 + 8 bits each way, the segmented norm
+                from uqdme_amd._lib import load
+                front, inv = EH.last_plan(load(), EH.QFL_FRONT), EH.last_plan(load(), EH.QFL_INVERSE)
+                assert EH.kernels(front) == EH.kernels(inv) == [EH.LOW16K, EH.HIGH256], (front, inv)
+                assert front["norm"] == EH.SEG_NORM
             assert np.array_equal(out[z[f"dpos{j}"]].view(np.uint32), z[f"douts{j}"].view(np.uint32))
             assert sha(out) == c["out_sha"]
             w = state_words()

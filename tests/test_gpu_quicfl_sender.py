@@ -13,6 +13,7 @@ import torch
 
 from oracle import uq_eden as E
 from oracle import uq_quicfl as Q
+from tests import eden_plan_hook as EH
 from tests import quicfl_plan_hook as H
 
 pytestmark = pytest.mark.gpu
@@ -209,12 +210,15 @@ def test_batch_states_and_many_messages(fx):
     msg, new = q.quicfl_compress(torch.from_numpy(x), nbits, seeds, [123] * n, sender=snd, px_states=states,
                                  _state_out=True)
     assert last_form(H.SENDER) == H.ONE_WAVE
+    from uqdme_amd._lib import load
+    assert EH.last_plan(load(), EH.QFL_FRONT)["norm"] == EH.CHAINS_WHOLE          # 300 messages of 2^14
     # the first 20 messages again as a few-message call (the jump path: every run's generator
     # blocks by jump-ahead, KQ0j): the same bits and end states as the batch's one-wave-per-
     # message kernel
     few, fnew = q.quicfl_compress(torch.from_numpy(x[:20]), nbits, seeds[:20], [123] * 20, sender=snd,
                                   px_states=states[:20], _state_out=True)
     assert last_form(H.SENDER) == H.JUMP
+    assert EH.last_plan(load(), EH.QFL_FRONT)["norm"] == EH.SEG_NORM
     assert torch.equal(few.X, msg.X[:20]) and torch.equal(few.exact_mask, msg.exact_mask[:20])
     assert torch.equal(few.scale, msg.scale[:20]) and torch.equal(few.exact_count, msg.exact_count[:20])
     for j in range(20):
@@ -222,7 +226,6 @@ def test_batch_states_and_many_messages(fx):
         assert torch.equal(few.exact_vals[j, :cnt], msg.exact_vals[j, :cnt]), j
     assert np.array_equal(fnew, new[:20])
     # and through the team kernel (scouts + runs, test hook 4): the same again
-    from uqdme_amd._lib import load
     prev = load().uq_test_set_quicfl_hooks(4)
     try:
         team, tnew = q.quicfl_compress(torch.from_numpy(x[:20]), nbits, seeds[:20], [123] * 20, sender=snd,
@@ -282,6 +285,11 @@ def test_fused_quantize_equals_compress_then_decompress(fx, hooks):
             out, fnew, sc = uqdme.quicfl_quantize(torch.from_numpy(x), nbits, seeds, rots, sender=snd,
                                                   recv_table=rz[f"recv{nbits}"], px_states=states)
             assert last_form(H.SENDER, hooks) == sform, (n, dim)
+            # the front's and the inverse's passes: 12 + 3, 12 + 1, 12 + 4 bits, one pass of 10
+            want = {20000: [12, 3], 4099: [12, 1], 1 << 16: [12, 4], 700: [10]}[dim]
+            front, inv = EH.last_plan(load(), EH.QFL_FRONT), EH.last_plan(load(), EH.QFL_INVERSE)
+            assert EH.bits(front) == EH.bits(inv) == want, (front, inv)
+            assert front["norm"] == (EH.SEG_NORM if dim >= 16384 else EH.CHAINS_WHOLE if dim > 700 else EH.CHAINS_GENERIC)
             assert out.cpu().numpy().view(np.uint32).tolist() == ref.view(np.uint32).tolist(), (nbits, n, dim)
             assert np.array_equal(fnew, new) and torch.equal(sc, msg.scale)
     finally:

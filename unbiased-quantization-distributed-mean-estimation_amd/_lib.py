@@ -31,6 +31,8 @@ SIGNATURES = {
     "uq_test_last_unbiased_plan": (ctypes.c_int, [_p, _i32]),
     "uq_test_biased_plan": (ctypes.c_int, [_i64, _i64, _i32, _i32, _i32, _p, _i32]),
     "uq_test_last_biased_plan": (ctypes.c_int, [_p, _i32]),
+    "uq_test_eden_plan": (ctypes.c_int, [_i32, _i64, _i64, _i32, _i32, _p, _i32]),
+    "uq_test_last_eden_plan": (ctypes.c_int, [_i32, _p, _i32]),
     "uq_mt_jump_host": (ctypes.c_int, [_p, _i64, _p]),
     "uq_legacy_draw_f32": (ctypes.c_int, [_p, _p, _p, _p, _i32, _f64, _f64, _i64, _i64, _p, _p, _i32]),
     "uq_legacy_test_params": (ctypes.c_int, [_i64, _i64, _p, _p]),

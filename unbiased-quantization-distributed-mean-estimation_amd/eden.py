@@ -207,22 +207,31 @@ class EdenMessage:
     dim: int
 
 
-def eden_compress(x, bits_per_dimension=1, seeds=None, *, generator=None) -> EdenMessage:
-    """EdenSender.compress (AS:355-376) for every row of x [n, d]."""
+def _prologue(x, bits_per_dimension, seeds, generator):
+    """(device, x as f32 [n, d] on it, bits, one seed per row): the senders' argument checks."""
     dev = _device()
     x = _as_device_f32_2d(x, dev)
-    n, d = x.shape
-    nb = _bits(bits_per_dimension)
-    s = _seeds(seeds, n, generator)
-    D = padded_dim(d)
-    bins = torch.empty((n, D), dtype=torch.uint8, device=dev)
-    scale = torch.empty(n, dtype=torch.float32, device=dev)
+    return dev, x, _bits(bits_per_dimension), _seeds(seeds, x.shape[0], generator)
+
+
+def _call(name, dev, seeds, n, d, D, nb, head, tail):
+    """uq_eden_<name>_sb(*head, n, d, nb, signs of D, sign rows, sign bits, *tail, workspace,
+    stream); nothing to run for an empty batch."""
     if n and d:
-        tab, rows, sb = _sign_rows_bits(s, D, dev)
+        tab, rows, sb = _sign_rows_bits(seeds, D, dev)
         ws = _ws(n, d, dev)
-        _lib.check(_lib.load().uq_eden_compress_f32_sb(_ptr(x), n, d, nb, _ptr(tab), _ptr(rows), _ptr(sb), _ptr(bins),
-                                                       _ptr(scale), _ptr(ws), ws.numel(), _stream_ptr(dev)),
-                   "uq_eden_compress_f32_sb")
+        fn = f"uq_eden_{name}_sb"
+        _lib.check(getattr(_lib.load(), fn)(*map(_ptr, head), n, d, nb, _ptr(tab), _ptr(rows), _ptr(sb), *map(_ptr, tail),
+                                            _ptr(ws), ws.numel(), _stream_ptr(dev)), fn)
+
+
+def eden_compress(x, bits_per_dimension=1, seeds=None, *, generator=None) -> EdenMessage:
+    """EdenSender.compress (AS:355-376) for every row of x [n, d]."""
+    dev, x, nb, s = _prologue(x, bits_per_dimension, seeds, generator)
+    n, d = x.shape
+    bins = torch.empty((n, padded_dim(d)), dtype=torch.uint8, device=dev)
+    scale = torch.empty(n, dtype=torch.float32, device=dev)
+    _call("compress_f32", dev, s, n, d, bins.shape[1], nb, (x,), (bins, scale))
     return EdenMessage(bins=bins, scale=scale, seeds=s, nbits=nb, dim=d)
 
 
@@ -234,29 +243,17 @@ def eden_decompress(msg: EdenMessage) -> torch.Tensor:
     n = bins.shape[0]
     d = msg.dim
     out = torch.empty((n, d), dtype=torch.float32, device=dev)
-    if n and d:
-        tab, rows, sb = _sign_rows_bits(torch.as_tensor(msg.seeds), bins.shape[1], dev)
-        ws = _ws(n, d, dev)
-        _lib.check(_lib.load().uq_eden_decompress_f32_sb(_ptr(bins), _ptr(scale), n, d, msg.nbits, _ptr(tab),
-                                                         _ptr(rows), _ptr(sb), _ptr(out), _ptr(ws), ws.numel(),
-                                                         _stream_ptr(dev)), "uq_eden_decompress_f32_sb")
+    _call("decompress_f32", dev, torch.as_tensor(msg.seeds), n, d, bins.shape[1], msg.nbits, (bins, scale), (out,))
     return out
 
 
 def eden_quantize(x, bits_per_dimension=1, seeds=None, *, return_scale: bool = False, generator=None):
     """EDEN_quantize_Hadamard for every row of x [n, d] (rotation seed per row)."""
-    dev = _device()
-    x = _as_device_f32_2d(x, dev)
+    dev, x, nb, s = _prologue(x, bits_per_dimension, seeds, generator)
     n, d = x.shape
-    nb = _bits(bits_per_dimension)
-    s = _seeds(seeds, n, generator)
     out = torch.empty((n, d), dtype=torch.float32, device=dev)
     scale = torch.empty(n, dtype=torch.float32, device=dev)
-    if n and d:
-        tab, rows, sb = _sign_rows_bits(s, padded_dim(d), dev)
-        ws = _ws(n, d, dev)
-        _lib.check(_lib.load().uq_eden_f32_sb(_ptr(x), _ptr(out), n, d, nb, _ptr(tab), _ptr(rows), _ptr(sb),
-                                              _ptr(scale), _ptr(ws), ws.numel(), _stream_ptr(dev)), "uq_eden_f32_sb")
+    _call("f32", dev, s, n, d, padded_dim(d), nb, (x, out), (scale,))
     return (out, scale) if return_scale else out
 
 
