@@ -208,16 +208,23 @@ def eden_quantize(x: np.ndarray, nbits: int, seed: int) -> np.ndarray:
     return eden_decompress(bins, scale, nbits, seed, x.shape[0])
 
 
-def quicfl_decompress(X: np.ndarray, recv_table: np.ndarray, h_len: int, prng_seed: int, exact_mask, exact_values,
-                      scale, rotation_seed: int, dim: int) -> np.ndarray:
-    """QuicFLReceiver.decompress (AS:526-535): h = torch.randint(0, h_len, (D,)) from a CPU
-    generator seeded with prng_seed (= MT19937 word % h_len), v = recv_table.take(X * h_len + h),
-    exact coordinates overwritten in index order, v / scale (f32), inverse RHT, [:dim]."""
+def quicfl_receive_pre(X: np.ndarray, recv_table: np.ndarray, h_len: int, prng_seed: int, exact_mask, exact_values,
+                       scale) -> np.ndarray:
+    """QuicFLReceiver.decompress before its inverse RHT (AS:526-532), for any number of
+    coordinates: h = torch.randint(0, h_len, (D,)) from a CPU generator seeded with prng_seed
+    (= MT19937 word % h_len), v = recv_table.take(X * h_len + h), the coordinates where
+    exact_mask != 0 overwritten with exact_values in index order, v / scale (f32)."""
     X = np.asarray(X, np.int64).reshape(-1)
     h = (mt19937(int(prng_seed), X.size) % np.uint32(h_len)).astype(np.int64)
     v = np.asarray(recv_table, f32).reshape(-1)[X * h_len + h].copy()
     if exact_mask is not None:
-        m = np.asarray(exact_mask, bool).reshape(-1)
+        m = np.asarray(exact_mask).reshape(-1) != 0
         v[m] = np.asarray(exact_values, f32).reshape(-1)
-    v = (v / f32(scale)).astype(f32)
+    return (v / f32(scale)).astype(f32)
+
+
+def quicfl_decompress(X: np.ndarray, recv_table: np.ndarray, h_len: int, prng_seed: int, exact_mask, exact_values,
+                      scale, rotation_seed: int, dim: int) -> np.ndarray:
+    """QuicFLReceiver.decompress (AS:526-535): quicfl_receive_pre, inverse RHT, [:dim]."""
+    v = quicfl_receive_pre(X, recv_table, h_len, prng_seed, exact_mask, exact_values, scale)
     return inverse_rht(v, rotation_seed)[:dim]

@@ -41,6 +41,16 @@ def sender_tables(b: int, x_len: int | None = None, h_len: int | None = None):
     return X.astype(np.float32), p.astype(np.float32)
 
 
+def recv_table(b: int, h_len: int) -> np.ndarray:
+    """A synthetic receiver table float32 [2^b, h_len] (the reference's are [2^b, 64 / 32 / 16]):
+    every entry a different multiple of 2^-12, rows in increasing bands, so a wrong row or a
+    wrong h reads another value."""
+    L = 1 << b
+    r = np.arange(L, dtype=np.int64)[:, None]
+    h = np.arange(int(h_len), dtype=np.int64)[None, :]
+    return ((2 * r - (L - 1)) * 2048 + h * 7 + 1).astype(np.float32) / np.float32(4096)
+
+
 def data_txt(b: int, **override) -> str:
     d = dict(DATA[b])
     d.update(override)

@@ -371,7 +371,6 @@ def test_jump_path_equals_one_wave_across_shapes(fx, n, dim):
     rng = np.random.default_rng(n * 1000 + dim % 997)
     form = H.TEAM if (n, dim) in ((1, 4096), (128, 1 << 14)) else H.JUMP
     x = (rng.standard_normal((n, dim)) * rng.uniform(0.5, 4, (n, 1))).astype(np.float32)
-    x[0, 1] = 1e4                                                 # an exact coordinate at least
     seeds = [int(s) for s in rng.integers(0, 100, n)]
     rots = [int(s) for s in rng.integers(0, 100, n)]
     g = torch.Generator()
@@ -398,6 +397,9 @@ def test_jump_path_equals_one_wave_across_shapes(fx, n, dim):
             (a, sa), (b, sb) = out[0], out[2]
             assert torch.equal(a.X, b.X) and torch.equal(a.exact_mask, b.exact_mask), (nbits, kw.keys())
             assert torch.equal(a.exact_count, b.exact_count) and torch.equal(a.scale, b.scale)
+            # about 2^-8 of the rotated coordinates are exact (AS:475-478): every row has some, so
+            # the runs' exact-value writes and their move into index order have work to do
+            assert a.X.shape[1] < 4096 or int(a.exact_count.min()) > 0, a.exact_count
             for j in range(n):
                 c = int(a.exact_count[j])
                 assert torch.equal(a.exact_vals[j, :c], b.exact_vals[j, :c]), j
@@ -417,7 +419,6 @@ def test_two_runs_per_message_at_900_messages(fx):
     n, dim, nbits = 900, 1 << 18, 1
     g = torch.Generator(device="cuda").manual_seed(9)
     x = torch.randn(n, dim, generator=g, device="cuda") * 2.0
-    x[0, 1] = 1e4
     seeds = list(range(n))
     rots = [int(s) for s in np.random.default_rng(9).integers(0, 100, n)]
     pxs = list(range(5000, 5000 + n))
@@ -437,6 +438,7 @@ def test_two_runs_per_message_at_900_messages(fx):
     (a, da), (b, db) = out[0], out[2]
     assert torch.equal(a.X, b.X) and torch.equal(a.exact_mask, b.exact_mask)
     assert torch.equal(a.exact_count, b.exact_count) and torch.equal(a.scale, b.scale)
+    assert int(a.exact_count.min()) > 0                           # exact coordinates in every row (D >= 4096)
     assert torch.equal(a.exact_dense(), b.exact_dense())
     assert torch.equal(da.view(torch.int32), db.view(torch.int32))
     # the receiver fused into the two-wave runs (QUICFL_quantize's path) gives the same batch
@@ -451,7 +453,23 @@ MATRIX_FORMS = {(1, 1024): (H.ONE_WAVE, H.ONE_WAVE), (3, 1024): (H.ONE_WAVE, H.O
                 (1, 8192): (H.JUMP, H.TEAM), (3, 8192): (H.JUMP, H.TEAM),
                 (1, 32768): (H.JUMP, H.JUMP), (3, 32768): (H.JUMP, H.JUMP), (342, 1 << 17): (H.JUMP, H.JUMP)}
 MATRIX_BITS = {700: 3, 4096: 4, 5000: 1, 20000: 2, 1 << 17: 1}
+# The inputs carry their exact coordinates naturally: about 2^-8 of a rotated and scaled vector lies
+# beyond T (AS:475-478).  (A planted spike does the opposite: it dominates the norm, so every
+# scaled coordinate sits near +-1.)  The seed of each dim's batch and the oracle's exact count of
+# each of its rows, found on the CPU; 700 takes another seed since default_rng(700)'s first row
+# has a single exact coordinate.
+MATRIX_SEED = {700: 702, 4096: 4096, 5000: 5000, 20000: 20000, 1 << 17: 1 << 17}
+MATRIX_EXACT = {700: [4, 8, 4], 4096: [8, 19, 15], 5000: [39, 33, 33], 20000: [130, 125, 147]}
 _matrix_cache = {}
+
+
+def _runs_with_exact(mask, plan, side, D):
+    """The runs of a plan's form that hold an exact coordinate of this row: the jump form's runs
+    of L rounds, the receiver team kernel's of ceil(nch / 7) rounds (a round: 624 coordinates)."""
+    nch = (D + 623) // 624
+    per = plan["L"] if plan["form"] == H.JUMP else (nch + 6) // 7
+    assert plan["form"] == H.JUMP or (plan["form"] == H.TEAM and side == H.RECEIVER), plan
+    return set((np.flatnonzero(mask) // 624 // per).tolist())
 
 
 def _matrix_inputs(dim, rz, rmeta):
@@ -461,7 +479,7 @@ def _matrix_inputs(dim, rz, rmeta):
     if dim in _matrix_cache:
         return _matrix_cache[dim]
     nbits, rows = MATRIX_BITS[dim], 342 if dim == 1 << 17 else 3
-    rng = np.random.default_rng(dim)
+    rng = np.random.default_rng(MATRIX_SEED[dim])
     seeds = [int(s) for s in rng.integers(0, 100, rows)]
     rots = [int(s) for s in rng.integers(0, 200, rows)]
     g = torch.Generator()
@@ -473,7 +491,6 @@ def _matrix_inputs(dim, rz, rmeta):
     oracle = None
     if rows == 3:
         x = (rng.standard_normal((rows, dim)) * rng.uniform(0.5, 3, (rows, 1))).astype(np.float32)
-        x[:, 5] = 500.0                                                   # an exact coordinate in every row
         tX, tp = sender_tables(nbits)
         oracle = []
         for j in range(rows):
@@ -482,10 +499,11 @@ def _matrix_inputs(dim, rz, rmeta):
             rec = E.quicfl_decompress(exp["X"], rz[f"recv{nbits}"], rmeta["tables"][str(nbits)]["h_len"], exp["prng_seed"],
                                       exp["exact_indeces"], exp["exact_values"], exp["scale"], rots[j], dim)
             oracle.append((exp, gst, rec))
+        # the oracle alone: at least 2 exact coordinates in every row
+        assert [int(o[0]["exact_indeces"].sum()) for o in oracle] == MATRIX_EXACT[dim] and min(MATRIX_EXACT[dim]) >= 2
         x = torch.from_numpy(x)
     else:
         x = torch.randn(rows, dim, generator=torch.Generator(device="cuda").manual_seed(17), device="cuda") * 2.0
-        x[:, 5] = 500.0
     if oracle is not None:                                                # (the 180 MB batch has one case)
         _matrix_cache[dim] = (x, seeds, rots, states, oracle)
     return x, seeds, rots, states, oracle
@@ -507,7 +525,9 @@ def test_every_form_equals_one_wave_and_oracle(fx, dim, n):
     kernel, 32768 both jump forms, 342 x 2^17 the two-wave runs of both -- for uint8 and int64 X
     and the fused quantize.  The form is asserted through the plan hook; X, mask, exact values,
     counts, scales, end states and the decompressed batch equal the one-wave kernels' (hook 2)
-    bit for bit, and up to 20000 coordinates the oracle's."""
+    bit for bit, and up to 20000 coordinates the oracle's.  Every oracle row holds at least 2
+    exact coordinates (MATRIX_EXACT), from D = 8192 in at least two runs of each side's form, so
+    the runs' exact-value writes and compact slot bases have work to do."""
     import uqdme_amd.quicfl as q
     from uqdme_amd._lib import load
     meta, z, rmeta, rz = fx
@@ -528,6 +548,8 @@ def test_every_form_equals_one_wave_and_oracle(fx, dim, n):
                 out = q.quicfl_decompress_messages(m, rt)
                 assert last_form(H.RECEIVER, hooks) == (H.ONE_WAVE if hooks else rform)
                 res[hooks, dt] = (m, st, out)
+                if not hooks:
+                    plans = {side: H.last_plan(load(), side) for side in (H.SENDER, H.RECEIVER)}
             res[hooks, "fused"] = q.quicfl_quantize(x, nbits, seeds, rots, sender=snd, recv_table=rt, px_states=states)
             assert last_form(H.SENDER, hooks) == (H.ONE_WAVE if hooks else sform)
             if not hooks and sform == H.JUMP:
@@ -546,11 +568,19 @@ def test_every_form_equals_one_wave_and_oracle(fx, dim, n):
         assert torch.equal(fo.view(torch.int32), wave[2].view(torch.int32)), hooks
         assert np.array_equal(fst, wave[1]) and torch.equal(fsc, wave[0].scale), hooks
     if oracle is None:
+        assert int(res[0, torch.int64][0].exact_count.min()) >= 1
         return
     m, st, out = res[0, torch.int64]
     out = out.cpu().numpy()
     for j in range(n):
         exp, gst, rec = oracle[j]
+        # at least 2 exact coordinates in the oracle's row and in the GPU's message; from D = 8192
+        # in at least two runs of each side's form (the jump form's R runs of L rounds, the
+        # receiver team kernel's 7 of ceil(nch / 7)), so the runs' compact slot bases differ
+        assert int(exp["exact_indeces"].sum()) >= 2 and int(m.exact_count[j]) >= 2, j
+        if D >= 8192:
+            for side in (H.SENDER, H.RECEIVER):
+                assert len(_runs_with_exact(exp["exact_indeces"], plans[side], side, D)) >= 2, (j, side)
         assert np.array_equal(m.X[j].cpu().numpy(), exp["X"]), j
         assert np.array_equal(m.exact_mask[j].cpu().numpy(), exp["exact_indeces"]), j
         cnt = int(m.exact_count[j])
