@@ -536,6 +536,36 @@ int uq_eden_norm_workspace_bytes(int64_t n, int64_t D, size_t* bytes_out);
 int uq_eden_norm_f32(const float* v, int64_t n, int64_t D, int32_t mode, float* nrm, void* ws, size_t ws_bytes,
                      void* stream);
 
+/* ---- Scalar and DRIVE baselines: torch.rand_like from the global generator ---------------
+ * Scalar_quantize (All_Schemes.py:755-790) and DRIVE_quantize_Hadamard (AS:707-752) for n
+ * clients [n][d], bit-identical to the reference on torch CPU (tests/golden/rand_schemes_vectors.*).
+ * torch.rand_like takes one MT19937 word per element in index order, u = f32(w & 0xFFFFFF) *
+ * 2^-24.  px_state / px_seeds / px_state_out are uq_quicfl_compress_f32's: client j's generator
+ * as [n][UQ_QFL_STATE_WORDS] states or as seeds of fresh generators, and the state after the
+ * client's words.  d <= 2^28; n = 0 or d = 0 is a no-op.  Workspace: uq_rand_workspace_bytes.
+ *
+ * uq_scalar_quantize_f32: mn = min(x), mx = max(x) (NaN if x holds one), den = mx - mn.
+ *   den == 0: out = x, info[j] = UQ_SCALAR_CONSTANT, no word taken (px_state_out[j] is the input
+ *   state).  Else d words: q = clamp((x - mn) / den, 0, 1); t = q * nlevels; fl = floor(t);
+ *   out = ((fl + (u < t - fl)) / nlevels) * den + mn, every step one f32 operation.  nlevels is
+ *   the f32 of 2^bits - 1; below 1 the reference returns its input, so the call is refused.
+ * uq_drive_hadamard_f32: chunks of 2048; a chunk of L coordinates is zero-padded to P, the next
+ *   power of two, and takes P words: D = (u > 0.5) * 2 - 1.  The reference's "Hadamard" maps each
+ *   adjacent pair (a, b) to (a + b, (a + b) - b), log2(P) times (its views alias).  S =
+ *   f32(norm(x)^2) / (sum|Rx| + 1e-12f) with torch's norm and sum orders; out = pairsteps(S *
+ *   sign(Rx)) * D.  S_out [n][ceil(d / 2048)] (or NULL) receives each chunk's S.
+ *   uq_drive_words(d): the words one client takes, (d / 2048) * 2048 + pow2ceil(d % 2048)
+ *   (no last term when d % 2048 == 0); host only. */
+#define UQ_SCALAR_CONSTANT 1
+int uq_rand_workspace_bytes(int64_t n, int64_t d, size_t* bytes_out);
+int uq_drive_words(int64_t d, int64_t* words_out);
+int uq_scalar_quantize_f32(const float* x, float* out, int64_t n, int64_t d, float nlevels, const uint32_t* px_state,
+                           const int32_t* px_seeds, uint32_t* px_state_out, int32_t* info, void* ws, size_t ws_bytes,
+                           void* stream);
+int uq_drive_hadamard_f32(const float* x, float* out, int64_t n, int64_t d, const uint32_t* px_state,
+                          const int32_t* px_seeds, uint32_t* px_state_out, float* S_out, void* ws, size_t ws_bytes,
+                          void* stream);
+
 /* After the stream has been synchronised: UQ_OK, or UQ_E_TIMEOUT if any
  * inter-workgroup wait in a previous call on this workspace gave up. Clears it. */
 int uq_check_status(void* ws, void* stream);

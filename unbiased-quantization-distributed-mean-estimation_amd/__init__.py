@@ -18,6 +18,7 @@ from .eden import (EDEN_quantize_Hadamard, eden_quantize, eden_compress, eden_de
                    randomized_hadamard_transform, randomized_inverse_hadamard_transform)
 from .quicfl import (QuicFLReceiver, QuicFLSender, QuicFLMessages, QUICFL_quantize, quicfl_compress,
                      quicfl_decompress, quicfl_decompress_messages, quicfl_quantize, set_tables_prefix)
+from .rand_schemes import Scalar_quantize, DRIVE_quantize_Hadamard, scalar_quantize, drive_quantize, drive_words
 from ._lib import UQError, load as load_library, library_path
 from .distributed import ShardedDME, shard_range, sharded_client_mean, sharded_quantize_mean
 from .dme import DISTRIBUTIONS, Suspended, legacy_draw, nmse_simulation
@@ -26,6 +27,7 @@ from .fl_stats import compute_nmse_stats_auto, data_format, round_nmse
 from .outpool import set_output_pool
 
 __all__ = [
+    "Scalar_quantize", "DRIVE_quantize_Hadamard", "scalar_quantize", "drive_quantize", "drive_words",
     "QuicFLReceiver", "QuicFLSender", "QuicFLMessages", "QUICFL_quantize", "quicfl_compress", "quicfl_decompress",
     "quicfl_decompress_messages", "quicfl_quantize", "set_tables_prefix",
     "RATE_TABLE", "rate_to_m", "Type_unbiased_quantize", "quantize_dequantize", "client_mean",

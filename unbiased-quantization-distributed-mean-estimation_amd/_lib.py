@@ -82,7 +82,13 @@ SIGNATURES = {
     "uq_eden_f32_sb": (ctypes.c_int, [_p, _p, _i64, _i64, _i32, _p, _p, _p, _p, _p, _sz, _p]),
     "uq_eden_norm_workspace_bytes": (ctypes.c_int, [_i64, _i64, ctypes.POINTER(_sz)]),
     "uq_eden_norm_f32": (ctypes.c_int, [_p, _i64, _i64, _i32, _p, _p, _sz, _p]),
-    "uq_tc_bound": (ctypes.c_int, [_i64, ctypes.POINTER(_sz)]),
+    "uq_rand_workspace_bytes": (ctypes.c_int, [_i64, _i64, ctypes.POINTER(_sz)]),
+    "uq_drive_words": (ctypes.c_int, [_i64, ctypes.POINTER(_i64)]),
+    # x, out, n, d, nlevels, px_state, px_seeds, px_state_out, info, ws, ws_bytes, stream
+    "uq_scalar_quantize_f32": (ctypes.c_int, [_p, _p, _i64, _i64, _f32, _p, _p, _p, _p, _p, _sz, _p]),
+    # x, out, n, d, px_state, px_seeds, px_state_out, S_out, ws, ws_bytes, stream
+    "uq_drive_hadamard_f32": (ctypes.c_int, [_p, _p, _i64, _i64, _p, _p, _p, _p, _p, _sz, _p]),
+    "uq_tc_bound":(ctypes.c_int, [_i64, ctypes.POINTER(_sz)]),
     "uq_tc_workspace_bytes": (ctypes.c_int, [_i64, _i64, ctypes.POINTER(_sz)]),
     "uq_tc_encode": (ctypes.c_int, [_p, _p, _i64, _i64, _i64, _i32, _p, _sz, _p, _p, _sz, _p]),
     "uq_tc_decode": (ctypes.c_int, [_p, _sz, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p]),

@@ -62,7 +62,7 @@ int uq_internal::side_stream(SideStream** out) {
 
 extern "C" {
 
-int uq_version(void) { return 102; }
+int uq_version(void) { return 103; }
 
 #ifndef UQ_BUILD_ID
 #define UQ_BUILD_ID "unknown"

@@ -1,6 +1,6 @@
 // uq_internal.h — host functions and state that cross the library's translation units.
 //
-// Each scheme is one .hip (uq_unbiased.hip, uq_biased.hip, uq_eden.hip, uq_quicfl.hip,
+// Each scheme is one .hip (uq_unbiased.hip, uq_biased.hip, uq_eden.hip, uq_quicfl.hip, uq_rand.hip,
 // uq_codec.hip) beside the host core, uq_core.hip.  What they share on the host is declared
 // here and defined in exactly one of them, so every piece of state (the error string, the side
 // streams) exists once in the library.  Nothing here is exported: the

@@ -20,8 +20,9 @@ Type_biased_quantize (ND:139-140, no draws), QUICFL_quantize (ND:141-142: one ra
 for the message seed, then D words of the same generator for bernoulli(p_X), AS:489 -- the host
 advances a copy of the CPU generator past those words and hands each message its generator
 state, so the batched sender draws exactly the reference's words; tables from `quicfl=(sender,
-receiver)` or the drop-in's prefix).  DRIVE / Kashin / Scalar are not built, so the draw stream
-equals that of a driver calling only the selected schemes.
+receiver)` or the drop-in's prefix).  Kashin is not built, and DRIVE and Scalar (rand_schemes.py:
+drop-ins and px_states batch forms) are not wired into this loop, so the draw stream equals that
+of a driver calling only the selected schemes.
 """
 from __future__ import annotations
 
