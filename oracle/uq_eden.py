@@ -120,7 +120,9 @@ def inverse_rht(v: np.ndarray, seed: int) -> np.ndarray:
 
 
 def torch_norm2(v: np.ndarray) -> f32:
-    """torch.norm(v, 2) on CPU f32: 8 lanes of fma accumulation, lanes in order, tail, sqrt."""
+    """torch.norm(v, 2) on CPU f32: 8 lanes of fma accumulation over the first L - L % 8 elements,
+    lanes in order, then the tail (the next 4 by mul + add when at least 4 remain, what is left
+    after that by fma), sqrt."""
     v = np.asarray(v, f32)
     n = v.shape[0] - v.shape[0] % 8
     acc = np.zeros(8, np.float64)
@@ -132,14 +134,18 @@ def torch_norm2(v: np.ndarray) -> f32:
     s = accf[0]
     for j in range(1, 8):
         s = f32(s + accf[j])
-    # below one 8-wide vector torch takes other paths (measured, torch 2.10): |x| for one
-    # element, fma for two, mul + add for four
+    # measured, torch 2.10: |x| for one element, fma for two; after the whole 8-wide vectors a
+    # 4-wide step by mul + add when 4 elements remain, then the last 1 to 3 by fma
     if v.shape[0] == 1:
         return f32(abs(v[0]))
     if v.shape[0] == 2:
         return f32(np.sqrt(f32(np.float64(f32(np.float64(v[0]) * v[0])) + np.float64(v[1]) * v[1])))
+    if v.shape[0] - n >= 4:
+        for t in v[n:n + 4]:
+            s = f32(s + f32(t * t))
+        n += 4
     for t in v[n:]:
-        s = f32(s + f32(t * t))
+        s = f32(np.float64(s) + np.float64(t) * np.float64(t))
     return f32(np.sqrt(s))
 
 

@@ -190,7 +190,7 @@ void uqo_client_mean_acc(const float* q, int64_t n, int64_t d, float n_div, floa
 
 /* torch.norm(v, 2) on CPU f32, the EDEN sender's norm (NMSE_Results/Codes/All_Schemes.py:329):
  * 8 lanes of fma chains over the first d - d % 8 elements, lanes added in order, the tail
- * as f32 v*v adds, sqrt.  The C form of oracle/uq_eden.py:torch_norm2 (pinned there against
+ * (4 by f32 v*v adds when 4 remain, the rest by fma), sqrt.  The C form of oracle/uq_eden.py:torch_norm2 (pinned there against
  * torch; tests/test_oracle_golden.py checks both against torch.norm). */
 float uqo_torch_norm2(const float* v, int64_t d) {
     float acc[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
@@ -199,15 +199,19 @@ float uqo_torch_norm2(const float* v, int64_t d) {
         for (int l = 0; l < 8; ++l) acc[l] = fmaf(v[i + l], v[i + l], acc[l]);
     float s = acc[0];
     for (int l = 1; l < 8; ++l) s = s + acc[l];
-    /* below one 8-wide vector torch takes other paths (measured, torch 2.10): |x| for one
-     * element, fma for two, mul + add for four; ragged tails after whole vectors are not
-     * pinned (EDEN's D is a power of two) */
+    /* measured, torch 2.10: |x| for one element, fma for two; after the whole 8-wide vectors a
+     * 4-wide step by mul + add when 4 elements remain, then the last 1 to 3 by fma (pinned
+     * at every d in 1..72 and ragged d up to 2047, tests/test_norm_oracle.py: DRIVE's last
+     * chunk has any length) */
     if (d == 1) return fabsf(v[0]);
     if (d == 2) return sqrtf(fmaf(v[1], v[1], fmaf(v[0], v[0], 0.0f)));
-    for (int64_t i = nv; i < d; ++i) {
-        const float p = v[i] * v[i];
-        s = s + p;
-    }
+    int64_t i = nv;
+    if (d - i >= 4)
+        for (const int64_t e = i + 4; i < e; ++i) {
+            const float p = v[i] * v[i];
+            s = s + p;
+        }
+    for (; i < d; ++i) s = fmaf(v[i], v[i], s);
     return sqrtf(s);
 }
 

@@ -1,8 +1,9 @@
 """NumPy restatement of the reference's Scalar_quantize (AS:755-790) and DRIVE_quantize_Hadamard
 (AS:707-752) on torch CPU, from the oracle's blocks: the MT19937 stream (uq_quicfl.mt_draw),
 torch's CPU sum (uq_oracle.torch_sum) and norm (uq_eden.torch_norm2).  Every step is one f32
-operation.  tests/test_rand_schemes_oracle.py pins it to the reference's own outputs
-(tests/golden/rand_schemes_vectors.*); the GPU tests compare the kernels with both.
+operation.  tests/test_rand_schemes_oracle.py and tests/test_rand_edges_oracle.py pin it to the
+reference's own outputs (tests/golden/rand_schemes_vectors.*, rand_schemes_edges.*); the GPU
+tests compare the kernels with both.
 
 A generator state is the oracle's (left, next, words[624]).
 """
@@ -77,8 +78,9 @@ def pair_steps(v: np.ndarray, k: int) -> np.ndarray:
     return v
 
 
-def drive_quantize(x, state):
-    """-> (out f32 [d], state after, words taken, S f32 [chunks])."""
+def drive_quantize(x, state, norm=torch_norm2):
+    """-> (out f32 [d], state after, words taken, S f32 [chunks]).  `norm`: the chunk norm
+    (AS:741), torch's order unless a test asks what another order would give."""
     x = np.asarray(x, f32)
     d = x.shape[0]
     out = np.empty(d, f32)
@@ -96,7 +98,7 @@ def drive_quantize(x, state):
             taken += P
             D = np.where(uniforms(words) > f32(0.5), f32(1), f32(-1)).astype(f32)
             Rx = pair_steps((D * vp).astype(f32), k)
-            nrm = torch_norm2(v)
+            nrm = norm(v)
             S = f32(f32(nrm * nrm) / f32(torch_sum(np.abs(Rx)) + f32(1e-12)))
             sg = (Rx > 0).astype(f32) - (Rx < 0).astype(f32)          # torch.sign: +0 at +-0
             Rh = (S * sg).astype(f32)
@@ -128,14 +130,39 @@ def gen_input(c) -> np.ndarray:
     elif kind == "zero_pairs":                 # zero pairs inside a live chunk
         v = rs.normal(0, 1, d)
         v[(np.arange(d) // 2) % 3 == 1] = 0.0
+    # ---- the edge fixture's kinds (tests/golden/make_golden_rand_edges.py) ----
+    elif kind == "nan_at":                     # one NaN at c["at"]
+        v = rs.normal(0, 1, d)
+        v[c["at"]] = np.nan
+    elif kind == "ninf_at":                    # one -inf at c["at"]
+        v = rs.normal(0, 1, d)
+        v[c["at"]] = -np.inf
+    elif kind == "pm_inf":                     # +inf and -inf together: max - min = inf
+        v = rs.normal(0, 1, d)
+        v[d // 3] = np.inf
+        v[2 * d // 3] = -np.inf
+    elif kind == "huge_span":                  # finite, max - min overflows
+        v = rs.normal(0, 1, d)
+        v[d // 4] = 3e38
+        v[3 * d // 4] = -3e38
+    elif kind == "subnormal":                  # every element subnormal in f32
+        v = rs.normal(0, 1, d) * 1e-41
+    elif kind == "normal_1e19":                # nrm * nrm overflows
+        v = rs.normal(0, 1, d) * 1e19
+    elif kind == "few_ulps":                   # a span of a few ulps of 1
+        v = 1 + np.abs(rs.normal(0, 1, d)) * 1e-7
+    elif kind == "neg_zero_third":             # -0.0 at every third element
+        v = rs.normal(0, 1, d)
+        v[::3] = -0.0
     else:
         raise ValueError(kind)
     return v.astype(f32)
 
 
-def load_fixture():
-    meta = json.load(open(os.path.join(GOLDEN, "rand_schemes_vectors.json")))
-    z = np.load(os.path.join(GOLDEN, "rand_schemes_vectors.npz"))
+def load_fixture(name="rand_schemes_vectors"):
+    """(meta, npz) of rand_schemes_vectors, or of rand_schemes_edges (make_golden_rand_edges.py)."""
+    meta = json.load(open(os.path.join(GOLDEN, name + ".json")))
+    z = np.load(os.path.join(GOLDEN, name + ".npz"))
     return meta, z
 
 

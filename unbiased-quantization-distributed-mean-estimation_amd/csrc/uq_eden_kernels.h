@@ -683,7 +683,11 @@ eden_norm_kernel(const float* __restrict__ v, int64_t n, int64_t D, float* __res
         if (tid < 8 * kNormClients && cl == 0 && vec < n) {
             const float* p = v + vec * D;
             // torch's CPU norm below one 8-wide vector (EDEN's D = 1, 2, 4): |x| for one
-            // element, fma for two, mul + add for four (measured on torch 2.10)
+            // element, fma for two, mul + add for four (measured on torch 2.10).  EDEN's D is a
+            // power of two, so the loop below only ever runs at D = 4.  At other D % 8 torch
+            // takes 4 by mul + add and the last 1 to 3 by fma (KR4 in uq_rand_kernels.h and
+            // oracle/uq_oracle.c uqo_torch_norm2 do): not restated here, where no caller and
+            // no test can reach it.
             if (D == 2) tot = fmaf(p[1], p[1], fmaf(p[0], p[0], 0.0f));
             else for (int64_t i = nv; i < D; ++i) tot = tot + p[i] * p[i];
             nrm[vec] = D == 1 ? fabsf(p[0]) : sqrtf(tot);

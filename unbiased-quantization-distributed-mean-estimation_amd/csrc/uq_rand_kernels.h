@@ -281,8 +281,9 @@ __device__ __forceinline__ void drive_pair_steps(float (&r)[8], int stages) {
 // thread t holds elements 8 t .. 8 t + 7 (threads at or beyond P / 8 only join the barriers).
 //   Rx = pairstep^log2(P)(D * v)                                              AS:737-738
 //   S = f32(nrm * nrm) / (sum|Rx| + 1e-12f)                                   AS:741
-//       nrm: torch.norm of the L inputs (KE2's order: 8 fma chains, lanes in order, the tail;
-//       |x| for L = 1, fma for L = 2), run by 8 lanes of wave 1 from LDS;
+//       nrm: torch.norm of the L inputs (8 fma chains over L - L % 8, lanes in order, then the
+//       tail: 4 by mul + add when 4 remain, the last 1 to 3 by fma; |x| for L = 1, fma for
+//       L = 2), run by 8 lanes of wave 1 from LDS;
 //       sum|Rx|: torch's CPU sum of P <= 2048 values (block_torch_sum)
 //   out = pairstep^log2(P)(S * sign(Rx)) * D, the first L                      AS:743-750
 __global__ void __launch_bounds__(kQBlock)
@@ -332,8 +333,17 @@ drive_chunk_kernel(const float* __restrict__ x, float* __restrict__ out, int64_t
         float tot = __shfl(acc, 0, kWave);
         for (int u = 1; u < 8; ++u) tot = tot + __shfl(acc, u, kWave);
         if (tid == kWave) {
-            if (L == 2) tot = fmaf(sv[1], sv[1], fmaf(sv[0], sv[0], 0.0f));
-            else for (int i = 8 * steps; i < L; ++i) tot = tot + sv[i] * sv[i];
+            if (L == 2) {
+                tot = fmaf(sv[1], sv[1], fmaf(sv[0], sv[0], 0.0f));
+            } else {                                  // L % 8 left: 4 by mul + add when 4 remain, the rest by fma
+                int i = 8 * steps;
+                if (L - i >= 4)
+                    for (const int e = i + 4; i < e; ++i) {
+                        const float p = sv[i] * sv[i];
+                        tot = tot + p;
+                    }
+                for (; i < L; ++i) tot = fmaf(sv[i], sv[i], tot);
+            }
             snrm = L == 1 ? fabsf(sv[0]) : sqrtf(tot);
         }
     }

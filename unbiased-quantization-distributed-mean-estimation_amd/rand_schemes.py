@@ -18,7 +18,8 @@ with `generator=` its clients run one after another, each waiting for the state 
 left: px_states is its batch form.  DRIVE always takes drive_words(d), so with `generator=` the
 host places every client by jump-ahead and the batch runs at once.
 
-Bit-identical to the reference on torch CPU (tests/golden/rand_schemes_vectors.*).
+Bit-identical to the reference on torch CPU (tests/golden/rand_schemes_vectors.* and
+rand_schemes_edges.*).
 """
 from __future__ import annotations
 
