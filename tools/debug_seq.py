@@ -4,20 +4,20 @@ import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 import uqdme
-from uqdme_amd import quantizer as Q
+from uqdme_amd import _runtime as RT
 from oracle import uq_oracle as O, uq_oracle_c as C
 from tests import golden_data as G
 
 def ctrl():
     key = (0, torch.cuda.current_stream().cuda_stream)
-    ws = Q._ws_cache[key]
+    ws = RT._ws_cache[key]
     return ws[:8].view(torch.int32).cpu().tolist(), ws.numel(), ws.data_ptr()
 
 def run(sp, pos=None, qs=None, poison=False):
     x = G.spec_gen(sp)
     m = O.rate_to_m(sp["R"], sp["d"])
     if poison:
-        for ws in Q._ws_cache.values():
+        for ws in RT._ws_cache.values():
             ws.random_(0, 255)
     got = uqdme.quantize_dequantize(torch.from_numpy(x[None]).cuda(), m=m, X=[sp["X"]], torch_threads=sp["threads"])
     torch.cuda.synchronize()

@@ -16,7 +16,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 
 def main():
     import uqdme
-    from uqdme_amd import quantizer
+    from uqdme_amd import _runtime
     L = ctypes.CDLL(os.path.join(HERE, "libexp_norm_pitch_pf.so"))
     L.exp_norm_pitch.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
                                  ctypes.c_int, ctypes.c_void_p]
@@ -27,7 +27,7 @@ def main():
     seeds = torch.randint(0, 100, (n,), generator=torch.Generator().manual_seed(5))
     uqdme.eden_compress(x, 1, seeds=seeds)
     torch.cuda.synchronize()
-    ws = next(iter(quantizer._ws_cache.values()))
+    ws = next(iter(_runtime._ws_cache.values()))
     vptr = ws.data_ptr() + 256                                 # EdenLayout.vec_off = kCtrlBytes
     nrm = torch.empty(n, device="cuda")
     sp = torch.cuda.current_stream().cuda_stream

@@ -17,17 +17,13 @@ indices instead (identical whenever info flag 1 is clear; see include/uq_dme.h).
 """
 from __future__ import annotations
 
-import ctypes
-import functools
 import threading
 
-import numpy as np
 import torch
 
-from . import _lib
-from .quantizer import (_as_device_f32_2d, _device, _ptr, _resolve_m, _stream_ptr, _workspace,
-                        check_status, get_torch_threads)
-from .rates import RATE_TABLE
+from . import _lib, _runtime
+from ._runtime import as_batch_f32, as_vector_f32, check_status, get_torch_threads, ptr, stream_ptr, workspace_for
+from .rates import RATE_TABLE, rate_to_m
 
 __all__ = ["Type_biased_quantize", "biased_quantize", "TIES_TORCH", "TIES_LOWEST_INDEX",
            "FLAG_AMBIGUOUS", "FLAG_NONFINITE", "FLAG_RANGE", "FLAG_TORCH_TIES"]
@@ -46,13 +42,6 @@ _TIES = {"torch": TIES_TORCH, "lowest": TIES_LOWEST_INDEX, TIES_TORCH: TIES_TORC
          TIES_LOWEST_INDEX: TIES_LOWEST_INDEX}
 
 
-@functools.lru_cache(maxsize=256)
-def _biased_ws_bytes(n: int, d: int, T: int) -> int:
-    out = ctypes.c_size_t(0)
-    _lib.check(_lib.load().uq_biased_workspace_bytes(n, d, T, ctypes.byref(out)), "uq_biased_workspace_bytes")
-    return int(out.value)
-
-
 def biased_quantize(x, bits_per_dimension=1, *, m: int | None = None, torch_threads: int | None = None,
                     ties="torch", out=None, return_l1: bool = False, return_info: bool = False,
                     host_check: bool = False):
@@ -63,10 +52,10 @@ def biased_quantize(x, bits_per_dimension=1, *, m: int | None = None, torch_thre
     host_check (torch ties): the call may wait once for the number of rows whose tie choice
     needs the replay and skips the replay's kernels when there are none (UQ_TIES_HOST_CHECK:
     for synchronous few-row callers; the same bits either way)."""
-    dev = _device()
-    x = _as_device_f32_2d(x, dev)
+    dev = _runtime.device()
+    x = as_batch_f32(x, dev)
     n, d = x.shape
-    mm = _resolve_m(bits_per_dimension, m, d)
+    mm = int(m) if m is not None else rate_to_m(bits_per_dimension, d)
     T = get_torch_threads() if torch_threads is None else int(torch_threads)
     if ties not in _TIES:
         raise ValueError("ties must be 'torch' or 'lowest'")
@@ -76,10 +65,10 @@ def biased_quantize(x, bits_per_dimension=1, *, m: int | None = None, torch_thre
         raise ValueError("out must be a contiguous f32 tensor like x")
     l1_out = torch.empty(n, dtype=torch.float32, device=dev) if return_l1 else None
     info = torch.empty((n, 2), dtype=torch.int32, device=dev) if return_info else None
-    ws = _workspace(dev, _biased_ws_bytes(n, d, T))
+    ws = workspace_for("uq_biased_workspace_bytes", dev, n, d, T)
     policy = _TIES[ties] | (_HOST_CHECK if host_check and _TIES[ties] == TIES_TORCH else 0)
-    _lib.check(_lib.load().uq_type_biased_f32(_ptr(x), _ptr(out), n, d, mm, T, policy, _ptr(l1_out),
-                                              _ptr(info), _ptr(ws), ws.numel(), _stream_ptr(dev)),
+    _lib.check(_lib.load().uq_type_biased_f32(ptr(x), ptr(out), n, d, mm, T, policy, ptr(l1_out),
+                                              ptr(info), ptr(ws), ws.numel(), stream_ptr(dev)),
                "uq_type_biased_f32")
     res = [out]
     if return_l1:
@@ -92,7 +81,7 @@ def biased_quantize(x, bits_per_dimension=1, *, m: int | None = None, torch_thre
 def _flags_and_status(dev, d: int, info) -> int:
     """One synchronisation for row 0's flags and this workspace's status word (uq_check_status's
     word at byte 8; check_status() would read every cached workspace of the stream)."""
-    ws = _workspace(dev, _biased_ws_bytes(1, d, get_torch_threads()))
+    ws = workspace_for("uq_biased_workspace_bytes", dev, 1, d, get_torch_threads())
     hw = getattr(_tls, "pinned", None)
     if hw is None:
         hw = _tls.pinned = torch.empty(2, dtype=torch.int32, pin_memory=True)
@@ -112,20 +101,13 @@ def Type_biased_quantize(input_vector, bits_per_dimension=1):
     reference raises when m' is not finite (AS:656); so does this.  AS:671 copies the input
     so as not to alias it; here the kernels only read it and the result is always a new
     tensor (d == 0 returns a clone), so no device-side copy is made."""
-    dev = _device()
+    dev = _runtime.device()
     l_rate = RATE_TABLE[bits_per_dimension]
-    if torch.is_tensor(input_vector):
-        v = input_vector.detach().to(device=dev, dtype=torch.float32)
-    else:
-        v = torch.tensor(np.asarray(input_vector), dtype=torch.float32, device=dev)
-    if v.dim() != 1:
-        raise RuntimeError("Type_biased_quantize expects a 1-D vector")
+    v = as_vector_f32(input_vector, dev, name="Type_biased_quantize")
     d = v.numel()
     m = int(l_rate * d)
     if d == 0:
         return v.clone()
-    if not v.is_contiguous():
-        v = v.contiguous()
     # below GRAIN the lowest-index rule runs as one launch (KB-small) and gives torch's bits
     # unless a threshold tie straddles the selection (flag 1): read the flags once and rerun
     # with the replay only then, so a tie-free call synchronises once

@@ -28,11 +28,15 @@ Serialized message (little endian):
 """
 from __future__ import annotations
 
+import ctypes
 import struct
 from dataclasses import dataclass
 
 import numpy as np
 import torch
+
+from . import _lib, _runtime
+from ._runtime import ptr, stream_ptr
 
 MAGIC = b"UQT1"
 VERSION = 1
@@ -143,8 +147,6 @@ class TypeMessages:
 
 
 def _tc_sizes(lib, n, d):
-    import ctypes
-    from . import _lib
     b = ctypes.c_size_t()
     _lib.check(lib.uq_tc_bound(d, ctypes.byref(b)), "uq_tc_bound")
     w = ctypes.c_size_t()
@@ -165,9 +167,7 @@ def encode_messages(tc: "TypeCodes", exact_zero_signs: bool = False,
     chunks through one staging buffer and workspace of that size, each chunk's exact bytes
     kept (one synchronisation per chunk): at 1024 x 2^20 the transient is ~0.5 GB instead of
     ~4.3 GB, and the returned buffer holds exactly the messages."""
-    from . import _lib
-    from .quantizer import _device, _ptr, _stream_ptr
-    dev = _device()
+    dev = _runtime.device()
     lib = _lib.load()
     codes = tc.codes.to(dev).contiguous()
     l1 = tc.l1.to(device=dev, dtype=torch.float32).contiguous()
@@ -178,8 +178,8 @@ def encode_messages(tc: "TypeCodes", exact_zero_signs: bool = False,
     chunk = n if n * bound <= staging_bytes else max(1, staging_bytes // max(1, bound))
 
     def encode(j0, nj, data, offsets, ws):
-        _lib.check(lib.uq_tc_encode(_ptr(codes[j0:j0 + nj]), _ptr(l1[j0:j0 + nj]), nj, d, int(tc.m), flags,
-                                    _ptr(data), data.numel(), _ptr(offsets), _ptr(ws), ws.numel(), _stream_ptr(dev)),
+        _lib.check(lib.uq_tc_encode(ptr(codes[j0:j0 + nj]), ptr(l1[j0:j0 + nj]), nj, d, int(tc.m), flags,
+                                    ptr(data), data.numel(), ptr(offsets), ptr(ws), ws.numel(), stream_ptr(dev)),
                    "uq_tc_encode")
 
     if chunk >= n:
@@ -206,9 +206,7 @@ def encode_messages(tc: "TypeCodes", exact_zero_signs: bool = False,
 
 def decode_messages(msgs: TypeMessages) -> "TypeCodes":
     """UQR1 messages -> TypeCodes (device); raises if any message is malformed (synchronises)."""
-    from . import _lib
-    from .quantizer import _device, _ptr, _stream_ptr
-    dev = _device()
+    dev = _runtime.device()
     lib = _lib.load()
     n, d = msgs.n, msgs.d
     codes = torch.empty((n, d), dtype=torch.int8, device=dev)
@@ -217,8 +215,8 @@ def decode_messages(msgs: TypeMessages) -> "TypeCodes":
     status = torch.empty(max(1, n), dtype=torch.int32, device=dev)
     data = msgs.data.to(dev)
     offsets = msgs.offsets.to(dev)
-    _lib.check(lib.uq_tc_decode(_ptr(data), data.numel(), _ptr(offsets), n, d, int(msgs.m), _ptr(codes), _ptr(l1),
-                                _ptr(kmax), _ptr(status), _stream_ptr(dev)), "uq_tc_decode")
+    _lib.check(lib.uq_tc_decode(ptr(data), data.numel(), ptr(offsets), n, d, int(msgs.m), ptr(codes), ptr(l1),
+                                ptr(kmax), ptr(status), stream_ptr(dev)), "uq_tc_decode")
     bad = int(torch.count_nonzero(status[:n]).item()) if n else 0
     if bad:
         raise ValueError(f"{bad} malformed UQR1 message(s) (status {status[:n].cpu().numpy().tolist()[:8]})")

@@ -30,6 +30,10 @@ from typing import Callable, Optional
 import torch
 import torch.distributed as dist
 
+from . import _runtime
+from .pipeline import DMEPipeline
+from .quantizer import client_mean
+
 Fold = Callable[[torch.Tensor, float, Optional[torch.Tensor]], torch.Tensor]
 
 
@@ -73,7 +77,6 @@ def _isend(t, dst, group):
 
 
 def _default_fold(q: torch.Tensor, n_div: float, est: Optional[torch.Tensor]) -> torch.Tensor:
-    from .quantizer import client_mean
     if est is None:
         return client_mean(q, n_div)
     return client_mean(q, n_div, est=est, accumulate=True)
@@ -157,7 +160,6 @@ class ShardedDME:
         if mode == "ordered" and pipeline == "encode":
             raise ValueError("mode 'ordered' folds q: use pipeline 'codes' or 'q'")
         if pipe is None:
-            from .pipeline import DMEPipeline
             pipe = DMEPipeline(n_local, d, bits_per_dimension, m=m, torch_threads=torch_threads, pipeline=pipeline,
                                device=device)
         self.pipe = pipe
@@ -238,9 +240,8 @@ def sharded_quantize_mean(x_local: torch.Tensor, bits_per_dimension, X_local, n_
 
     x_local = the rank's contiguous client block (see shard_range); X_local = its
     slice of the per-client uniforms drawn once for all clients."""
-    from .quantizer import _as_device_f32_2d, _device
-    dev = _device()
-    x_local = _as_device_f32_2d(x_local, dev)
+    dev = _runtime.device()
+    x_local = _runtime.as_batch_f32(x_local, dev)
     n_local, d = x_local.shape
     X_local = torch.as_tensor(X_local, dtype=torch.float32).reshape(-1).to(dev)
     sh = ShardedDME(n_local, d, n_total, bits_per_dimension, torch_threads=torch_threads, pipeline="q", mode=mode,

@@ -28,16 +28,20 @@ from __future__ import annotations
 
 import ctypes
 import os
+import queue
+import threading
 import time
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
 
 from . import _lib
+from ._mtstate import advance_generator, generator_words, set_generator_words
 from .biased import biased_quantize
-from .eden import eden_compress, eden_decompress, eden_quantize
+from .eden import eden_compress, eden_decompress, eden_quantize, padded_dim
 from .quantizer import client_mean, quantize_dequantize
-from .quicfl import quicfl_quantize
+from .quicfl import _dropin_pair, quicfl_quantize
 
 SCHEME_ORDER = ("eden", "unbiased", "biased", "quicfl")     # ND:135-142 call order
 
@@ -140,9 +144,6 @@ def _draw_ahead(dist: str, users, num_instances: int, dim: int, rs, device=None,
       * the caller quantizes the previous batch meanwhile.
     Host memory: three buffers of max(users) * dim f32, plus the draw's f64 values of the batch
     being drawn (8 n * dim bytes, pooled inside the library)."""
-    import queue
-    import threading
-
     total = len(users) * num_instances
     stop = threading.Event()
     nmax = max(users) if len(users) else 0
@@ -243,7 +244,6 @@ def _client_draws(gen, n, order, rates, qD):
     (which ends where the reference's loop leaves torch's global generator): EDEN's rotation
     seed (AS:797), unbiased's X (AS:634), QUIC-FL's prng seed (AS:820), its generator state, and
     its D bernoulli(p_X) words skipped by jump-ahead (AS:489)."""
-    from .quicfl import advance_generator, generator_words
     draws = {(sc, r): [] for sc in order for r in rates}
     for _ in range(n):
         for sc in order:
@@ -273,7 +273,6 @@ def _client_draws_parallel(gen, n, order, rates, qD, pool):
     -- one jump-ahead from the instance's first state -- and its QUIC-FL skips are jumps too;
     the jumps (uq_mt_jump_host, ~0.6 ms each, outside the GIL) overlap.  Same values and the same
     end state as the sequential loop (tests/test_dme_draws.py)."""
-    from .quicfl import advance_generator, generator_words, set_generator_words
     if n == 0:
         return {(sc, r): [] for sc in order for r in rates}
     st, w0 = generator_words(gen)
@@ -319,8 +318,6 @@ def nmse_simulation(dist: str = "normal", dim: int = 2048, users=USERS_ND, num_i
             raise ValueError(f"unknown scheme {sc!r}")
     order = [sc for sc in SCHEME_ORDER if sc in schemes]
     if "quicfl" in order:
-        from .eden import padded_dim
-        from .quicfl import _dropin_pair
         qsend, qrecv = quicfl if quicfl is not None else _dropin_pair()
         qD = padded_dim(dim)
     rs = np.random.RandomState(seed)                 # legacy stream == np.random.seed(seed)
@@ -340,7 +337,6 @@ def nmse_simulation(dist: str = "normal", dim: int = 2048, users=USERS_ND, num_i
             for sc, r in keys:
                 script[(sc, r)][:] = ck[f"script_{sc}_{r}"]
     t_start = time.perf_counter()
-    from concurrent.futures import ThreadPoolExecutor
     jump_pool = None
     if "quicfl" in order:
         jump_pool = ThreadPoolExecutor(max_workers=max(1, min(8, host_threads() // 2)))

@@ -18,16 +18,14 @@ so outputs agree to 1e-6 relative.  Only the 1- and 2-bit tables exist in the re
 """
 from __future__ import annotations
 
-import ctypes
 import threading
 import weakref
 from dataclasses import dataclass
 
-import numpy as np
 import torch
 
-from . import _lib
-from .quantizer import _as_device_f32_2d, _as_device_vec, _device, _ptr, _stream_ptr, _workspace
+from . import _lib, _runtime
+from ._runtime import as_batch_f32, as_vector_f32, ptr, stream_ptr, workspace_for
 
 __all__ = ["EDEN_quantize_Hadamard", "eden_quantize", "eden_compress", "eden_decompress", "EdenMessage",
            "rht_signs", "padded_dim", "randomized_hadamard_transform", "randomized_inverse_hadamard_transform"]
@@ -95,10 +93,10 @@ def padded_dim(d: int) -> int:
 
 def rht_signs(seeds, D: int, device=None) -> torch.Tensor:
     """int8 [len(seeds), D] RHT diagonals (AS:117-120) generated on the GPU."""
-    dev = device or _device()
+    dev = device or _runtime.device()
     s = torch.as_tensor(seeds, dtype=torch.int32).reshape(-1).to(dev)
     out = torch.empty((s.numel(), D), dtype=torch.int8, device=dev)
-    _lib.check(_lib.load().uq_rht_signs(_ptr(s), s.numel(), D, _ptr(out), _stream_ptr(dev)), "uq_rht_signs")
+    _lib.check(_lib.load().uq_rht_signs(ptr(s), s.numel(), D, ptr(out), stream_ptr(dev)), "uq_rht_signs")
     return out
 
 
@@ -150,7 +148,7 @@ def rht_sign_bits(tab: torch.Tensor) -> torch.Tensor:
     -1), which the EDEN passes that apply the diagonal read instead of the int8 rows."""
     rows, D = tab.shape
     out = torch.empty((rows, (D + 31) // 32), dtype=torch.int32, device=tab.device)
-    _lib.check(_lib.load().uq_rht_sign_bits(_ptr(tab), rows, D, _ptr(out), _stream_ptr(tab.device)),
+    _lib.check(_lib.load().uq_rht_sign_bits(ptr(tab), rows, D, ptr(out), stream_ptr(tab.device)),
                "uq_rht_sign_bits")
     return out
 
@@ -175,12 +173,6 @@ def _sign_rows_bits(seeds: torch.Tensor, D: int, dev):
     """(table, row index per client, the table's rows as bits)."""
     tab, rows = _sign_rows(seeds, D, dev)
     return tab, rows, _bits_for(tab)
-
-
-def _ws(n, d, dev):
-    b = ctypes.c_size_t(0)
-    _lib.check(_lib.load().uq_eden_workspace_bytes(n, d, ctypes.byref(b)), "uq_eden_workspace_bytes")
-    return _workspace(dev, int(b.value))
 
 
 def _seeds(seeds, n, generator=None):
@@ -209,8 +201,8 @@ class EdenMessage:
 
 def _prologue(x, bits_per_dimension, seeds, generator):
     """(device, x as f32 [n, d] on it, bits, one seed per row): the senders' argument checks."""
-    dev = _device()
-    x = _as_device_f32_2d(x, dev)
+    dev = _runtime.device()
+    x = as_batch_f32(x, dev)
     return dev, x, _bits(bits_per_dimension), _seeds(seeds, x.shape[0], generator)
 
 
@@ -219,10 +211,10 @@ def _call(name, dev, seeds, n, d, D, nb, head, tail):
     stream); nothing to run for an empty batch."""
     if n and d:
         tab, rows, sb = _sign_rows_bits(seeds, D, dev)
-        ws = _ws(n, d, dev)
+        ws = workspace_for("uq_eden_workspace_bytes", dev, n, d)
         fn = f"uq_eden_{name}_sb"
-        _lib.check(getattr(_lib.load(), fn)(*map(_ptr, head), n, d, nb, _ptr(tab), _ptr(rows), _ptr(sb), *map(_ptr, tail),
-                                            _ptr(ws), ws.numel(), _stream_ptr(dev)), fn)
+        _lib.check(getattr(_lib.load(), fn)(*map(ptr, head), n, d, nb, ptr(tab), ptr(rows), ptr(sb), *map(ptr, tail),
+                                            ptr(ws), ws.numel(), stream_ptr(dev)), fn)
 
 
 def eden_compress(x, bits_per_dimension=1, seeds=None, *, generator=None) -> EdenMessage:
@@ -237,7 +229,7 @@ def eden_compress(x, bits_per_dimension=1, seeds=None, *, generator=None) -> Ede
 
 def eden_decompress(msg: EdenMessage) -> torch.Tensor:
     """EdenReceiver.decompress (AS:383-413) for every row."""
-    dev = _device()
+    dev = _runtime.device()
     bins = msg.bins.to(dev).contiguous()
     scale = msg.scale.to(device=dev, dtype=torch.float32).contiguous()
     n = bins.shape[0]
@@ -258,8 +250,8 @@ def eden_quantize(x, bits_per_dimension=1, seeds=None, *, return_scale: bool = F
 
 
 def _rht(x, seeds, inverse: bool):
-    dev = _device()
-    x = _as_device_f32_2d(x, dev)
+    dev = _runtime.device()
+    x = as_batch_f32(x, dev)
     n, d = x.shape
     D = padded_dim(d)
     if inverse and d != D:
@@ -270,9 +262,9 @@ def _rht(x, seeds, inverse: bool):
     out = torch.empty((n, D), dtype=torch.float32, device=dev)
     if n and d:
         tab, rows = _sign_rows(s, D, dev)
-        ws = _ws(n, D, dev)
-        _lib.check(_lib.load().uq_rht_f32(_ptr(x), _ptr(out), n, d, int(inverse), _ptr(tab), _ptr(rows), _ptr(ws),
-                                          ws.numel(), _stream_ptr(dev)), "uq_rht_f32")
+        ws = workspace_for("uq_eden_workspace_bytes", dev, n, D)
+        _lib.check(_lib.load().uq_rht_f32(ptr(x), ptr(out), n, d, int(inverse), ptr(tab), ptr(rows), ptr(ws),
+                                          ws.numel(), stream_ptr(dev)), "uq_rht_f32")
     return out
 
 
@@ -291,8 +283,8 @@ def EDEN_quantize_Hadamard(input_vector, bits_per_dimension=1):
     """Drop-in for AS:792 (same name for the drivers' result keys).  Draws the rotation
     seed from torch's global CPU generator like the CPU reference (AS:797) and returns a
     NumPy f32 array (AS:811)."""
-    dev = _device()
-    v = _as_device_vec(input_vector, dev)
+    dev = _runtime.device()
+    v = as_vector_f32(input_vector, dev)
     seed = int(torch.randint(0, _SEEDS, (1,)).item())
     out = eden_quantize(v.view(1, -1), bits_per_dimension, seeds=[seed])
     # the NumPy result comes back through pinned memory (torch's caching host allocator):

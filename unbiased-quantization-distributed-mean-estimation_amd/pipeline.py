@@ -35,48 +35,45 @@ mode (INTEGRATION.md).
 Every launch goes through the C-ABI (include/uq_dme.h); nothing here computes on the CPU."""
 from __future__ import annotations
 
-import ctypes
 import statistics
 
 import torch
 
-from . import _lib
-from .rates import rate_to_m
+from . import _lib, _runtime
+from ._runtime import ptr
+from .rates import RATE_TABLE, rate_to_m
 
 __all__ = ["DMEPipeline", "PIPELINES", "codes4_fits"]
 
 PIPELINES = ("codes", "q", "encode", "codes4")
 
 
+def _codes4_shape(n: int, d: int) -> bool:
+    """The stream form's shape rule: n >= 256 and d a multiple of 4096, at most 2^29."""
+    return n >= 256 and d % 4096 == 0 and d <= (1 << 29)
+
+
 def codes4_fits(n: int, d: int, bits_per_dimension=1) -> bool:
     """The 4-bit code pipeline's shape conditions, and a rate whose counts stay <= 7 for
     Gaussian-like clients (m <= 0.64 d: R <= 2)."""
-    from .rates import RATE_TABLE
-    return n >= 256 and d % 4096 == 0 and d <= (1 << 29) and RATE_TABLE.get(bits_per_dimension, 1e9) <= 0.64
-
-
-def _p(t) -> int:
-    return 0 if t is None else t.data_ptr()
+    return _codes4_shape(n, d) and RATE_TABLE.get(bits_per_dimension, 1e9) <= 0.64
 
 
 class DMEPipeline:
     def __init__(self, n: int, d: int, bits_per_dimension=1, *, m: int | None = None, torch_threads: int = 1,
                  pipeline: str = "codes", device=None):
-        if not torch.cuda.is_available():
-            raise RuntimeError("uqdme requires a ROCm GPU (no CPU fallback by design)")
+        current = _runtime.device()                     # raises without a GPU
         if pipeline not in PIPELINES:
             raise ValueError(f"pipeline must be one of {PIPELINES}")
-        if pipeline == "codes4" and not (n >= 256 and d % 4096 == 0 and d <= (1 << 29)):
+        if pipeline == "codes4" and not _codes4_shape(n, d):
             raise ValueError("pipeline 'codes4' needs n >= 256 and d a multiple of 4096 (<= 2^29)")
-        self.dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.dev = current if device is None else torch.device(device)
         self.n, self.d = int(n), int(d)
         self.m = int(m) if m is not None else rate_to_m(bits_per_dimension, d)
         self.T = int(torch_threads)
         self.pipeline = pipeline
         self.lib = _lib.load()
-        b = ctypes.c_size_t()
-        _lib.check(self.lib.uq_workspace_bytes(self.n, self.d, self.T, ctypes.byref(b)), "uq_workspace_bytes")
-        self.ws_bytes = int(b.value)
+        self.ws_bytes = _runtime.workspace_bytes("uq_workspace_bytes", self.n, self.d, self.T)
         self.ws = torch.zeros(max(self.ws_bytes, 1 << 16), dtype=torch.uint8, device=self.dev)
         self.l1 = torch.empty(self.n, dtype=torch.float32, device=self.dev)
         self.kmax = torch.zeros(self.n, dtype=torch.int32, device=self.dev)
@@ -130,7 +127,7 @@ class DMEPipeline:
 
     # ---- the three launches ----------------------------------------------------------
     def l1_norms(self, x):
-        _lib.check(self.lib.uq_l1_torch_order_f32(_p(x), self.n, self.d, self.T, _p(self.l1), _p(self.ws),
+        _lib.check(self.lib.uq_l1_torch_order_f32(ptr(x), self.n, self.d, self.T, ptr(self.l1), ptr(self.ws),
                                                   self.ws_bytes, self._stream()), "uq_l1_torch_order_f32")
 
     def quantize(self, x, X, q=None, codes=None, pipeline: str | None = None):
@@ -142,20 +139,20 @@ class DMEPipeline:
             raise ValueError("this pipeline holds no q buffer")
         if pl == "codes4":
             nib = self._codes_for(pl) if codes is None else codes
-            _lib.check(self.lib.uq_type_unbiased_nibbles_ld_f32(_p(x), _p(q), max(self._ld(q), self.d), _p(nib),
-                                                                max(self._ld(nib), self.d // 2), _p(self.kmax), self.n,
-                                                                self.d, self.m, _p(X), _p(self.l1), None, self.T,
-                                                                _p(self.ws), self.ws_bytes, self._stream()),
+            _lib.check(self.lib.uq_type_unbiased_nibbles_ld_f32(ptr(x), ptr(q), max(self._ld(q), self.d), ptr(nib),
+                                                                max(self._ld(nib), self.d // 2), ptr(self.kmax), self.n,
+                                                                self.d, self.m, ptr(X), ptr(self.l1), None, self.T,
+                                                                ptr(self.ws), self.ws_bytes, self._stream()),
                        "uq_type_unbiased_nibbles_ld_f32")
             self._codes_valid = True
             self._nib_valid = True
             return
         self._nib_valid = False
         codes = (self._codes_for(pl) if codes is None else codes) if pl != "q" else None
-        _lib.check(self.lib.uq_type_unbiased_codes_ld_f32(_p(x), _p(q), max(self._ld(q), self.d), _p(codes),
+        _lib.check(self.lib.uq_type_unbiased_codes_ld_f32(ptr(x), ptr(q), max(self._ld(q), self.d), ptr(codes),
                                                           max(self._ld(codes), self.d),
-                                                          _p(self.kmax if codes is not None else None), self.n, self.d,
-                                                          self.m, _p(X), _p(self.l1), None, self.T, _p(self.ws),
+                                                          ptr(self.kmax if codes is not None else None), self.n, self.d,
+                                                          self.m, ptr(X), ptr(self.l1), None, self.T, ptr(self.ws),
                                                           self.ws_bytes, self._stream()),
                    "uq_type_unbiased_codes_ld_f32")
         self._codes_valid = codes is not None
@@ -166,21 +163,22 @@ class DMEPipeline:
         est = self.est if est is None else est
         if pl == "q":
             self._mean_without_q = False
-            _lib.check(self.lib.uq_client_mean_f32(_p(self.q), self.n, self.d, max(self._ld(self.q), self.d),
-                                                   float(n_div), int(bool(accumulate)), _p(est), self._stream()),
+            _lib.check(self.lib.uq_client_mean_f32(ptr(self.q), self.n, self.d, max(self._ld(self.q), self.d),
+                                                   float(n_div), int(bool(accumulate)), ptr(est), self._stream()),
                        "uq_client_mean_f32")
         elif pl == "codes4":
             self._mean_without_q = False
-            _lib.check(self.lib.uq_nibbles_q_mean_ld_f32(_p(self.nib), max(self._ld(self.nib), self.d // 2), _p(self.q),
-                                                         max(self._ld(self.q), self.d), _p(self.l1), _p(self.kmax),
-                                                         self.n, self.d, self.m, float(n_div), int(bool(accumulate)),
-                                                         _p(est), self._stream()), "uq_nibbles_q_mean_ld_f32")
+            _lib.check(self.lib.uq_nibbles_q_mean_ld_f32(ptr(self.nib), max(self._ld(self.nib), self.d // 2),
+                                                         ptr(self.q), max(self._ld(self.q), self.d), ptr(self.l1),
+                                                         ptr(self.kmax), self.n, self.d, self.m, float(n_div),
+                                                         int(bool(accumulate)), ptr(est), self._stream()),
+                       "uq_nibbles_q_mean_ld_f32")
         else:
             q = self.q if pl == "codes" else None
             self._mean_without_q = q is None
-            _lib.check(self.lib.uq_codes_q_mean_ld_f32(_p(self.codes), max(self._ld(self.codes), self.d), _p(q),
-                                                       max(self._ld(q), self.d), _p(self.l1), _p(self.kmax), self.n,
-                                                       self.d, self.m, float(n_div), int(bool(accumulate)), _p(est),
+            _lib.check(self.lib.uq_codes_q_mean_ld_f32(ptr(self.codes), max(self._ld(self.codes), self.d), ptr(q),
+                                                       max(self._ld(q), self.d), ptr(self.l1), ptr(self.kmax), self.n,
+                                                       self.d, self.m, float(n_div), int(bool(accumulate)), ptr(est),
                                                        self._stream()), "uq_codes_q_mean_ld_f32")
         return est
 
@@ -280,7 +278,7 @@ class DMEPipeline:
         """Synchronise; raise if an in-kernel wait timed out, or if the last mean was taken
         from codes alone (pipeline "encode", or a step overridden to it) while a client's
         codes overflowed, since its est contribution is then wrong."""
-        _lib.check(self.lib.uq_check_status(_p(self.ws), self._stream()), "uq_check_status")
+        _lib.check(self.lib.uq_check_status(ptr(self.ws), self._stream()), "uq_check_status")
         if self._mean_without_q and self.overflowed():
             raise OverflowError("type codes overflowed (lattice counts > 127) in an encode-only step: "
                                 "est is wrong for those clients; use pipeline='codes' (falls back to q)")

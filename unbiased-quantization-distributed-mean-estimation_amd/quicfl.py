@@ -25,7 +25,6 @@ from __future__ import annotations
 import ast
 import ctypes
 import os
-import struct
 import threading
 from dataclasses import dataclass
 from types import SimpleNamespace
@@ -33,14 +32,15 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _runtime
+from ._mtstate import (STATE_WORDS, advance_generator, generator_words, set_generator_words,  # noqa: F401
+                       upload_generators)
+from ._runtime import as_batch_f32, as_vector_f32, ptr, stream_ptr, workspace_for
 from .eden import _sign_rows, padded_dim, randomized_inverse_hadamard_transform
-from .quantizer import _as_device_f32_2d, _as_device_vec, _device, _ptr, _stream_ptr, _workspace
 
 __all__ = ["QuicFLReceiver", "QuicFLSender", "QuicFLMessages", "QUICFL_quantize", "quicfl_compress",
            "quicfl_decompress", "quicfl_decompress_messages", "quicfl_quantize", "prng_seed", "set_tables_prefix"]
 
-STATE_WORDS = 626                  # UQ_QFL_STATE_WORDS: (left, next, 624 words)
 _FLAG_P, _FLAG_INDEX, _FLAG_PX, _FLAG_X, _FLAG_TIMEOUT, _FLAG_EXACT, _FLAG_RECV_INDEX = 1, 2, 4, 8, 16, 32, 64  # UQ_QFL_*
 _tables_prefix = None
 _USE_PACKED = os.environ.get("UQDME_QUICFL_PACKED", "1") == "1"     # the 4-byte table when it is valid
@@ -70,60 +70,12 @@ def prng_seed(seed) -> int:
     return int(_lib.load().uq_xxh64(b, len(b), 0)) % (1 << 16)
 
 
-# ---- torch CPU generator state <-> (left, next, 624 words) --------------------------------------
-def generator_words(gen: torch.Generator):
-    """(get_state() bytes, uint32 [626] = left, next, state words) of a CPU generator."""
-    st = gen.get_state().numpy().copy()
-    _, left, _, nxt = struct.unpack_from("<QiiQ", st.tobytes(), 0)
-    out = np.empty(STATE_WORDS, np.uint32)
-    out[0], out[1] = left, nxt
-    out[2:] = np.frombuffer(st[24:24 + 624 * 8].tobytes(), dtype=np.uint64).astype(np.uint32)
-    return st, out
-
-
-def set_generator_words(gen: torch.Generator, st: np.ndarray, words: np.ndarray) -> None:
-    b = bytearray(st.tobytes())
-    struct.pack_into("<i", b, 8, int(words[0]))
-    struct.pack_into("<Q", b, 16, int(words[1]))
-    b[24:24 + 624 * 8] = np.asarray(words[2:], np.uint32).astype(np.uint64).tobytes()
-    gen.set_state(torch.frombuffer(bytearray(b), dtype=torch.uint8).clone())
-
-
-def advance_generator(gen: torch.Generator, nwords: int) -> None:
-    """Leave the CPU generator where `nwords` 32-bit draws leave it -- torch.rand(nwords,
-    generator=gen) on CPU takes one word per f32 element, so this stands for the D bernoulli(p_X)
-    words of AS:489 -- by MT19937 jump-ahead (uq_mt_jump_host) instead of drawing them."""
-    if nwords < 0:
-        raise ValueError("nwords must be >= 0")
-    st, w = generator_words(gen)
-    left, nxt = int(w[0]), int(w[1])
-    rem = left - 1                                   # words left in the current block
-    if nwords <= rem:
-        w[0], w[1] = left - nwords, nxt + nwords
-    else:
-        after = nwords - rem                         # words read from the following blocks
-        k = (after + 623) // 624                     # twists
-        r = after - 624 * (k - 1)                    # words read from the last one (1..624)
-        out = np.empty(624, np.uint32)
-        key = np.ascontiguousarray(w[2:], np.uint32)
-        _lib.check(_lib.load().uq_mt_jump_host(key.ctypes.data, k, out.ctypes.data), "uq_mt_jump_host")
-        w[2:] = out
-        w[0], w[1] = 625 - r, r
-    set_generator_words(gen, st, w)
-
-
-def _check_state(words: np.ndarray) -> None:
-    left, nxt = int(words[0]), int(words[1])
-    if not 1 <= left <= 624 or (left > 1 and nxt != 625 - left):
-        raise ValueError("generator state with left/next outside ATen mt19937's invariant")
-
-
 # ---- sender ------------------------------------------------------------------------------------------
 class QuicFLSender:
     """AS:429-503 with the same constructor arguments and compress(data) contract."""
 
     def __init__(self, device=None, bits=(1, 2, 3, 4), sr_bits=(6, 5, 4, 4), prefix=None, tables=None):
-        self.device = device if device is not None else _device()
+        self.device = device if device is not None else _runtime.device()
         self.sender_table_X, self.sender_table_p, self.data, self.half_table_size = {}, {}, {}, {}
         self._xp = {}
         if tables is not None:                      # {nbits: (table_X, table_p, data dict)}
@@ -250,38 +202,6 @@ class QuicFLMessages:
         return dense
 
 
-def _ws(n, d, dev):
-    b = ctypes.c_size_t(0)
-    _lib.check(_lib.load().uq_quicfl_workspace_bytes(n, d, ctypes.byref(b)), "uq_quicfl_workspace_bytes")
-    return _workspace(dev, int(b.value))
-
-
-def _send_inputs(ps, n, px_seeds, px_states, dev):
-    """The small per-message inputs in ONE host-to-device copy (prng seeds, then the generator
-    states or the px seeds): each pageable copy would otherwise wait for the stream on its own.
-    -> (prng seeds, states or None, px seeds or None, state words out)."""
-    if px_states is not None:
-        w = np.asarray(px_states, np.uint32).reshape(n, STATE_WORDS)
-        for r in w:
-            _check_state(r)
-        tail = w.view(np.int32).reshape(-1)
-    else:
-        if px_seeds is None:
-            raise ValueError("px_seeds or px_states is required")
-        pxs = np.asarray(torch.as_tensor(px_seeds, dtype=torch.int64).reshape(-1).numpy(), np.int64)
-        if pxs.size != n:
-            raise ValueError("one px seed per message")
-        tail = (pxs & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
-    hin = np.empty(n + tail.size, np.int32)
-    hin[:n] = ps.numpy().astype(np.int32)
-    hin[n:] = tail
-    din = torch.from_numpy(hin).to(dev)
-    ps_d, tail_d = din[:n], din[n:]
-    if px_states is not None:
-        return ps_d, tail_d.view(n, STATE_WORDS), None, n * STATE_WORDS
-    return ps_d, None, tail_d, 0
-
-
 def _raise_send_flags(flags: int) -> None:
     if flags & _FLAG_P:
         raise RuntimeError("Expected p_in >= 0 && p_in <= 1 to be true, but got false.")   # AS:484 bernoulli
@@ -297,20 +217,22 @@ def _raise_send_flags(flags: int) -> None:
 
 def _send_prologue(x, nbits, seeds, rotation_seeds, sender, px_seeds, px_states, words):
     """What quicfl_compress and quicfl_quantize do before their call: the batch on the device, the
-    seeds hashed to prng seeds (AS:457), the per-message inputs (_send_inputs), `words` zeroed
+    seeds hashed to prng seeds (AS:457), the small per-message inputs in ONE host-to-device copy
+    (the prng seeds in front of the generator states or px seeds, upload_generators), `words` zeroed
     int32 per message (the flags first) with the end states behind them, and -- for a batch that
     is not empty -- the C call's leading, generator and trailing arguments (sign rows, tables
     and workspace; `keep` holds their tensors)."""
-    dev = _device()
+    dev = _runtime.device()
     dd = sender.data[nbits]
-    x = _as_device_f32_2d(x, dev)
+    x = as_batch_f32(x, dev)
     n, d = x.shape
     s = [int(v) for v in torch.as_tensor(seeds).reshape(-1).tolist()] if not isinstance(seeds, (list, tuple)) else list(seeds)
     rs = torch.as_tensor(rotation_seeds, dtype=torch.int64).reshape(-1)
     if len(s) != n or rs.numel() != n:
         raise ValueError("one seed and one rotation seed per message")
     ps = torch.tensor([prng_seed(v) for v in s], dtype=torch.int64)
-    ps_d, st_in, pxs_d, nst = _send_inputs(ps, n, px_seeds, px_states, dev)
+    ps_d, st_in, pxs_d = upload_generators(n, px_states, px_seeds, dev, "message", head=ps.numpy().astype(np.int32))
+    nst = n * STATE_WORDS if st_in is not None else 0
     dout = torch.zeros(words * n + nst, dtype=torch.int32, device=dev)
     a = SimpleNamespace(dev=dev, x=x, n=n, d=d, D=padded_dim(d), h_len=int(dd["h_len"]), rs=rs, ps=ps, nst=nst, dout=dout,
                         info=dout[:n], st_out=dout[words * n:].view(n, STATE_WORDS) if nst else None)
@@ -318,12 +240,12 @@ def _send_prologue(x, nbits, seeds, rotation_seeds, sender, px_seeds, px_states,
         tab, rows = _sign_rows(rs, a.D, dev)
         xp = sender.table_xp(nbits, dev)
         tp = sender.table_packed(nbits, dev) if _USE_PACKED else None
-        ws = _ws(n, d, dev)
+        ws = workspace_for("uq_quicfl_workspace_bytes", dev, n, d)
         a.keep = (tab, rows, xp, tp, ws, ps_d, st_in, pxs_d)
-        a.head = (_ptr(x), n, d, _ptr(tab), _ptr(rows), _ptr(xp), _ptr(tp), xp.shape[0], a.h_len,
+        a.head = (ptr(x), n, d, ptr(tab), ptr(rows), ptr(xp), ptr(tp), xp.shape[0], a.h_len,
                   float(np.float32(dd["delta"])))
-        a.gens = (_ptr(ps_d), _ptr(st_in), _ptr(pxs_d), _ptr(a.st_out))
-        a.tail = (_ptr(ws), ws.numel(), _stream_ptr(dev))
+        a.gens = (ptr(ps_d), ptr(st_in), ptr(pxs_d), ptr(a.st_out))
+        a.tail = (ptr(ws), ws.numel(), stream_ptr(dev))
     return a
 
 
@@ -346,8 +268,8 @@ def quicfl_compress(x, nbits: int, seeds, rotation_seeds, *, sender: QuicFLSende
     hout = np.zeros(a.dout.numel(), np.int32)
     if n and a.d:
         _lib.check(_lib.load().uq_quicfl_compress_f32(
-            *a.head, *a.gens, _ptr(X), 0 if x_dtype == torch.int64 else 1, _ptr(mask), _ptr(ev), _ptr(a.dout[n:2 * n]),
-            _ptr(scale), _ptr(a.info), *a.tail), "uq_quicfl_compress_f32")
+            *a.head, *a.gens, ptr(X), 0 if x_dtype == torch.int64 else 1, ptr(mask), ptr(ev), ptr(a.dout[n:2 * n]),
+            ptr(scale), ptr(a.info), *a.tail), "uq_quicfl_compress_f32")
         hout = a.dout.cpu().numpy()
         _raise_send_flags(int(np.bitwise_or.reduce(hout[:n])) if n else 0)
     msg = QuicFLMessages(X=X, exact_mask=mask, exact_vals=ev, exact_count=torch.from_numpy(hout[n:2 * n].copy()),
@@ -371,7 +293,7 @@ def quicfl_decompress(X, nbits: int, prng_seeds, rotation_seeds, scale, dim: int
     index order in its first exact_count[j] entries (quicfl_compress's layout).  scale [n];
     returns [n, dim] f32.  Raises IndexError where torch.take would (AS:530) and RuntimeError
     when a compact row's count does not match its mask (AS:531)."""
-    dev = _device()
+    dev = _runtime.device()
     X = torch.as_tensor(X)
     if X.dim() == 1:
         X = X.view(1, -1)
@@ -418,9 +340,9 @@ def quicfl_decompress(X, nbits: int, prng_seeds, rotation_seeds, scale, dim: int
         _lib.check(L.uq_quicfl_receive_workspace_bytes(n, D, ctypes.byref(wb)), "uq_quicfl_receive_workspace_bytes")
         ws = torch.empty(max(int(wb.value), 1), dtype=torch.uint8, device=dev)
         _lib.check(L.uq_quicfl_receive_ws_f32(
-            _ptr(Xd), _X_KIND[Xd.dtype], n, D, _ptr(tab), rows, hl, _ptr(seeds32), _ptr(m), _ptr(v),
-            1 if (compact and m is not None) else 0, _ptr(cnt), _ptr(sc), _ptr(pre), _ptr(info), _ptr(ws), wb.value,
-            _stream_ptr(dev)), "uq_quicfl_receive_ws_f32")
+            ptr(Xd), _X_KIND[Xd.dtype], n, D, ptr(tab), rows, hl, ptr(seeds32), ptr(m), ptr(v),
+            1 if (compact and m is not None) else 0, ptr(cnt), ptr(sc), ptr(pre), ptr(info), ptr(ws), wb.value,
+            stream_ptr(dev)), "uq_quicfl_receive_ws_f32")
         if not _defer_check:
             _raise_recv_flags(int(np.bitwise_or.reduce(info.cpu().numpy())))
     out = randomized_inverse_hadamard_transform(pre, rs)[:, :dim]
@@ -447,7 +369,7 @@ class QuicFLReceiver:
     """AS:507-535 with the same constructor arguments and decompress(data) contract."""
 
     def __init__(self, device=None, bits=(1, 2, 3, 4), sr_bits=(6, 5, 4, 4), prefix=None, tables=None):
-        self.device = device if device is not None else _device()
+        self.device = device if device is not None else _runtime.device()
         self.recv_table = {}
         self._dev_tables = {}
         if tables is not None:                      # {nbits: [rows, h_len] tensor or array}
@@ -472,7 +394,7 @@ class QuicFLReceiver:
 
     def _table(self, nbits):
         """The receiver table on the device (copied once per device)."""
-        dev = _device()
+        dev = _runtime.device()
         key = ("_dev", int(nbits), dev.index)
         t = self._dev_tables.get(key)
         if t is None:
@@ -487,7 +409,7 @@ class QuicFLReceiver:
         mask = vals = cnt = None
         ei = data.get("exact_indeces")
         if ei is not None:
-            dev = _device()
+            dev = _runtime.device()
             mask = torch.as_tensor(ei).reshape(1, D).to(dev)
             ev = torch.as_tensor(data["exact_values"], dtype=torch.float32).reshape(-1)
             if ev.numel() == 1:
@@ -512,7 +434,7 @@ class QuicFLReceiver:
 
 def _dropin_pair():
     prefix = default_tables_prefix()
-    dev = _device()
+    dev = _runtime.device()
     key = (prefix, dev.index)
     with _dropin_lock:
         pair = _dropin.get(key)
@@ -536,7 +458,7 @@ def quicfl_quantize(x, nbits: int, seeds, rotation_seeds, *, sender: QuicFLSende
     scale = torch.empty(n, dtype=torch.float32, device=dev)
     if n and d:
         _lib.check(_lib.load().uq_quicfl_quantize_f32(
-            *a.head, _ptr(rt), rt.numel(), *a.gens, _ptr(out), _ptr(scale), _ptr(a.info), *a.tail), "uq_quicfl_quantize_f32")
+            *a.head, ptr(rt), rt.numel(), *a.gens, ptr(out), ptr(scale), ptr(a.info), *a.tail), "uq_quicfl_quantize_f32")
     if _host_out:                          # the result and the flags / states in one synchronisation
         host = torch.empty(out.numel(), dtype=torch.float32, pin_memory=True)
         hsmall = torch.empty(dout.numel(), dtype=torch.int32, pin_memory=True)
@@ -567,8 +489,8 @@ def QUICFL_quantize(input_vector, bits_per_dimension=1):
     draw of the global CPU generator (the message seed), the sender (bernoulli(p_X) from the same
     generator, left where the reference leaves it) and the receiver fused in one pass
     (quicfl_quantize); returns a NumPy f32 array of length d."""
-    dev = _device()
-    v = _as_device_vec(input_vector, dev)
+    dev = _runtime.device()
+    v = as_vector_f32(input_vector, dev)
     sender, receiver = _dropin_pair()
     seed = int(torch.randint(0, 100, (1,)).item())
     nbits = bits_per_dimension

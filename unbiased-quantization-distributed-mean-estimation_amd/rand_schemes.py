@@ -9,7 +9,7 @@ torch.rand_like drawn from the global CPU generator (one MT19937 word per elemen
     scalar_quantize(x[n, d], bits, px_states= | px_seeds= | generator=) -> (q, new_states, info)
     drive_quantize(x[n, d], px_states= | px_seeds= | generator=)        -> (q, new_states[, S])
         the batch forms.  Client j's words come from px_states[j] ([626] = left, next, state
-        words of a torch CPU generator, see quicfl.generator_words), from a fresh generator seeded
+        words of a torch CPU generator, see _mtstate.generator_words), from a fresh generator seeded
         with px_seeds[j], or from `generator`, where client j starts where clients 0..j-1 leave the
         stream (the drivers' order) and the generator ends where the last client leaves it.
 
@@ -28,9 +28,9 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib
-from .quantizer import _as_device_f32_2d, _device, _ptr, _stream_ptr, _workspace
-from .quicfl import STATE_WORDS, _check_state, advance_generator, generator_words, set_generator_words
+from . import _lib, _runtime
+from ._mtstate import STATE_WORDS, advance_generator, generator_words, set_generator_words, upload_generators
+from ._runtime import as_batch_f32, as_vector_f32, ptr, stream_ptr, workspace_for
 
 __all__ = ["Scalar_quantize", "DRIVE_quantize_Hadamard", "scalar_quantize", "drive_quantize", "drive_words",
            "SCALAR_CONSTANT"]
@@ -43,27 +43,6 @@ def drive_words(d: int) -> int:
     w = ctypes.c_int64(0)
     _lib.check(_lib.load().uq_drive_words(int(d), ctypes.byref(w)), "uq_drive_words")
     return int(w.value)
-
-
-def _ws(n, d, dev):
-    b = ctypes.c_size_t(0)
-    _lib.check(_lib.load().uq_rand_workspace_bytes(n, d, ctypes.byref(b)), "uq_rand_workspace_bytes")
-    return _workspace(dev, int(b.value))
-
-
-def _gen_inputs(n, px_states, px_seeds, dev):
-    """The clients' generators on the device in one copy -> (states or None, seeds or None)."""
-    if px_states is not None:
-        w = np.ascontiguousarray(np.asarray(px_states, np.uint32).reshape(n, STATE_WORDS))
-        for r in w:
-            _check_state(r)
-        return torch.from_numpy(w.view(np.int32)).to(dev), None
-    if px_seeds is None:
-        raise ValueError("px_states, px_seeds or generator is required")
-    s = np.asarray(torch.as_tensor(px_seeds, dtype=torch.int64).reshape(-1).numpy(), np.int64)
-    if s.size != n:
-        raise ValueError("one px seed per client")
-    return None, torch.from_numpy((s & 0xFFFFFFFF).astype(np.uint32).view(np.int32)).to(dev)
 
 
 def _one_source(px_states, px_seeds, generator):
@@ -81,8 +60,8 @@ def scalar_quantize(x, bits_per_dimension, *, px_states=None, px_seeds=None, gen
     A constant row comes back unchanged and its generator untouched.  2**bits - 1 < 1 (AS:772):
     q is a copy of x, no word is taken and new_states are the given ones (None for px_seeds)."""
     _one_source(px_states, px_seeds, generator)
-    dev = _device()
-    x = _as_device_f32_2d(x, dev)
+    dev = _runtime.device()
+    x = as_batch_f32(x, dev)
     n, d = x.shape
     nl = _nlevels(bits_per_dimension)
     if generator is not None:                       # the drivers' order: each client after the one before
@@ -99,13 +78,13 @@ def scalar_quantize(x, bits_per_dimension, *, px_states=None, px_seeds=None, gen
     if nl < 1 or n == 0 or d == 0:
         given = None if px_states is None else np.array(px_states, np.uint32).reshape(n, STATE_WORDS)
         return x.clone(), given, np.zeros(n, np.int32)
-    st_in, seeds = _gen_inputs(n, px_states, px_seeds, dev)
+    _, st_in, seeds = upload_generators(n, px_states, px_seeds, dev)
     q = torch.empty_like(x)
     dout = torch.empty(n * (1 + STATE_WORDS), dtype=torch.int32, device=dev)      # info, then the end states
-    ws = _ws(n, d, dev)
+    ws = workspace_for("uq_rand_workspace_bytes", dev, n, d)
     _lib.check(_lib.load().uq_scalar_quantize_f32(
-        _ptr(x), _ptr(q), n, d, float(np.float32(nl)), _ptr(st_in), _ptr(seeds), _ptr(dout[n:]), _ptr(dout), _ptr(ws),
-        ws.numel(), _stream_ptr(dev)), "uq_scalar_quantize_f32")
+        ptr(x), ptr(q), n, d, float(np.float32(nl)), ptr(st_in), ptr(seeds), ptr(dout[n:]), ptr(dout), ptr(ws),
+        ws.numel(), stream_ptr(dev)), "uq_scalar_quantize_f32")
     hout = dout.cpu().numpy()
     return q, hout[n:].reshape(n, STATE_WORDS).view(np.uint32).copy(), hout[:n].copy()
 
@@ -116,8 +95,8 @@ def drive_quantize(x, *, px_states=None, px_seeds=None, generator=None, return_s
     S [n, ceil(d / 2048)] (AS:741).  Every client takes drive_words(d) words.  Nothing here
     waits for the GPU."""
     _one_source(px_states, px_seeds, generator)
-    dev = _device()
-    x = _as_device_f32_2d(x, dev)
+    dev = _runtime.device()
+    x = as_batch_f32(x, dev)
     n, d = x.shape
     if generator is not None:
         words = drive_words(d)
@@ -132,26 +111,16 @@ def drive_quantize(x, *, px_states=None, px_seeds=None, generator=None, return_s
     S = torch.empty((n, nch), dtype=torch.float32, device=dev) if return_scale else None
     st_out = torch.empty((n, STATE_WORDS), dtype=torch.int32, device=dev)
     if n and d:
-        st_in, seeds = _gen_inputs(n, px_states, px_seeds, dev)
-        ws = _ws(n, d, dev)
+        _, st_in, seeds = upload_generators(n, px_states, px_seeds, dev)
+        ws = workspace_for("uq_rand_workspace_bytes", dev, n, d)
         _lib.check(_lib.load().uq_drive_hadamard_f32(
-            _ptr(x), _ptr(q), n, d, _ptr(st_in), _ptr(seeds), _ptr(st_out), _ptr(S), _ptr(ws), ws.numel(),
-            _stream_ptr(dev)), "uq_drive_hadamard_f32")
+            ptr(x), ptr(q), n, d, ptr(st_in), ptr(seeds), ptr(st_out), ptr(S), ptr(ws), ws.numel(),
+            stream_ptr(dev)), "uq_drive_hadamard_f32")
     elif px_states is not None:
         st_out = torch.from_numpy(np.array(px_states, np.uint32).reshape(n, STATE_WORDS).view(np.int32)).to(dev)
     if generator is not None:
         generator.set_state(g.get_state())
     return (q, st_out, S) if return_scale else (q, st_out)
-
-
-def _dropin_vector(input_vector, dev, name):
-    if torch.is_tensor(input_vector):
-        v = input_vector.detach().to(device=dev, dtype=torch.float32)
-    else:
-        v = torch.tensor(np.asarray(input_vector), dtype=torch.float32, device=dev)
-    if v.dim() != 1:
-        raise RuntimeError(f"{name} expects a 1-D vector")
-    return v.contiguous()
 
 
 def Scalar_quantize(input_vector, bits_per_dimension=1):
@@ -160,8 +129,8 @@ def Scalar_quantize(input_vector, bits_per_dimension=1):
     which is left where the reference leaves it: d words on, or untouched when the vector is
     constant (AS:763) or 2**bits - 1 < 1 (AS:772), which return a copy.  Returns a new f32
     tensor of shape (d,) on the GPU; d = 0 returns an empty one."""
-    dev = _device()
-    v = _dropin_vector(input_vector, dev, "Scalar_quantize")
+    dev = _runtime.device()
+    v = as_vector_f32(input_vector, dev, name="Scalar_quantize")
     if v.numel() == 0 or _nlevels(bits_per_dimension) < 1:
         return v.clone()
     gen = torch.default_generator
@@ -176,8 +145,8 @@ def DRIVE_quantize_Hadamard(input_vector, bits_per_dimension=1):
     reference's pair steps, one scale per 2048-coordinate chunk, sign quantization and back.
     Takes drive_words(d) words of torch's global CPU generator, which is moved on by jump-ahead
     without waiting for the GPU.  Returns a new f32 tensor of shape (d,) on the GPU."""
-    dev = _device()
-    v = _dropin_vector(input_vector, dev, "DRIVE_quantize_Hadamard")
+    dev = _runtime.device()
+    v = as_vector_f32(input_vector, dev, name="DRIVE_quantize_Hadamard")
     if v.numel() == 0:
         return v.clone()
     gen = torch.default_generator
