@@ -566,6 +566,51 @@ int uq_drive_hadamard_f32(const float* x, float* out, int64_t n, int64_t d, cons
                           const int32_t* px_seeds, uint32_t* px_state_out, float* S_out, void* ws, size_t ws_bytes,
                           void* stream);
 
+/* ---- Kashin baseline: Kashin_quantize (All_Schemes.py:834-854) ----------------------------
+ * KashinStochasticQuantizationSender.compress (AS:249-261) and its receiver (AS:269-274) for n
+ * clients [n][dim], bit-identical to the reference on torch CPU (tests/golden/kashin_vectors.*).
+ * D = uq_kashin_padded_dim(dim) (AS:202-210, host only): a power of two doubles, another length
+ *   goes to the next power of two, doubled when dim / D > 0.85.  The entries take D and check it
+ *   (a power of two >= max(2, dim), <= 2^28).
+ * The loop (AS:212-239) runs on the device, nothing waits on the host: M = torch.norm(x) /
+ *   f32(sqrt(delta * D)); iteration i: b = RHT(residual padded to D) with diagonal row sign_row[j]
+ *   of signs [rows][D] (uq_rht_signs; the reference's rotation seed is 123), c += clamp(b, -M, M);
+ *   for i < niters - 1 the residual loses the clamped part's inverse transform and M *= f32(eta);
+ *   then err = norm(x - inverse(c)[:dim]) / norm(residual) and the client is done when err <
+ *   f32(err).  At i = 0 the two norms are the same bits and at i = niters - 1 the test changes
+ *   nothing, so it is evaluated for 0 < i < niters - 1 only.  Every norm is torch's CPU order for
+ *   one thread.  iters [n] = the forward transforms each client ran.
+ * The stochastic quantizer (AS:67-82) of c: mn = min(c), step = (max(c) - mn) / f32(nlevels - 1),
+ *   q = (c - mn) / step, bins = floor(q) + bernoulli(q - floor(q)); coordinate k takes word k of a
+ *   CPU generator seeded with xxh64(str(seed)) % 2^16 (uq_xxh64), the draw being f32(w & 0xFFFFFF)
+ *   * 2^-24 < p.  The stream is cut into runs of run_words coordinates, R = ceil(D / run_words) per
+ *   client, each walked by one wave from its own state: runs [rows][R][UQ_QFL_STATE_WORDS] u32 =
+ *   (left, next, state[624]) of the generator at each run's start, client j reading row run_row[j]
+ *   (run_row NULL: row j), so clients with one seed share a row.
+ * Outputs: bins [n][D] u8, mn [n], step [n], iters [n] and info [n] int32 flags: UQ_KASHIN_BAD_P
+ *   (some p is NaN or outside [0, 1], where the reference's torch.bernoulli raises RuntimeError: an
+ *   all-zero vector, a NaN or an inf, every vector of dim 1) and UQ_KASHIN_BIN_RANGE (a bin above
+ *   255, stored saturated; only nlevels = 256 can reach it).
+ * uq_kashin_decompress_f32: out [n][dim] = (H(mn + bins * step) * diag)[:dim], the product and
+ *   the sum rounded apart.  uq_kashin_f32: both fused, no message written; mn, step and iters may
+ *   be NULL there.  niters >= 1, nlevels in 2..256, delta > 0; n = 0 or dim = 0 is a no-op.
+ *   Workspace: uq_kashin_workspace_bytes(n, D). */
+#define UQ_KASHIN_BAD_P 1
+#define UQ_KASHIN_BIN_RANGE 2
+int uq_kashin_padded_dim(int64_t dim, int64_t* D_out);
+int uq_kashin_workspace_bytes(int64_t n, int64_t D, size_t* bytes_out);
+int uq_kashin_compress_f32(const float* x, int64_t n, int64_t dim, int64_t D, int32_t niters, double eta, double delta,
+                           double err, int32_t nlevels, const int8_t* signs, const int32_t* sign_row,
+                           const uint32_t* runs, const int32_t* run_row, int64_t run_words, uint8_t* bins, float* mn,
+                           float* step, int32_t* info, int32_t* iters, void* ws, size_t ws_bytes, void* stream);
+int uq_kashin_decompress_f32(const uint8_t* bins, const float* mn, const float* step, int64_t n, int64_t dim, int64_t D,
+                             const int8_t* signs, const int32_t* sign_row, float* out, void* ws, size_t ws_bytes,
+                             void* stream);
+int uq_kashin_f32(const float* x, float* out, int64_t n, int64_t dim, int64_t D, int32_t niters, double eta, double delta,
+                  double err, int32_t nlevels, const int8_t* signs, const int32_t* sign_row, const uint32_t* runs,
+                  const int32_t* run_row, int64_t run_words, float* mn, float* step, int32_t* info, int32_t* iters,
+                  void* ws, size_t ws_bytes, void* stream);
+
 /* After the stream has been synchronised: UQ_OK, or UQ_E_TIMEOUT if any
  * inter-workgroup wait in a previous call on this workspace gave up. Clears it. */
 int uq_check_status(void* ws, void* stream);

@@ -19,6 +19,8 @@ from .eden import (EDEN_quantize_Hadamard, eden_quantize, eden_compress, eden_de
 from .quicfl import (QuicFLReceiver, QuicFLSender, QuicFLMessages, QUICFL_quantize, quicfl_compress,
                      quicfl_decompress, quicfl_decompress_messages, quicfl_quantize, set_tables_prefix)
 from .rand_schemes import Scalar_quantize, DRIVE_quantize_Hadamard, scalar_quantize, drive_quantize, drive_words
+from .kashin import (Kashin_quantize, kashin_quantize, kashin_compress, kashin_decompress, kashin_padded_dim,
+                     KashinMessage)
 from ._lib import UQError, load as load_library, library_path
 from .distributed import ShardedDME, shard_range, sharded_client_mean, sharded_quantize_mean
 from .dme import DISTRIBUTIONS, Suspended, legacy_draw, nmse_simulation
@@ -27,6 +29,7 @@ from .fl_stats import compute_nmse_stats_auto, data_format, round_nmse
 from .outpool import set_output_pool
 
 __all__ = [
+    "Kashin_quantize", "kashin_quantize", "kashin_compress", "kashin_decompress", "kashin_padded_dim", "KashinMessage",
     "Scalar_quantize", "DRIVE_quantize_Hadamard", "scalar_quantize", "drive_quantize", "drive_words",
     "QuicFLReceiver", "QuicFLSender", "QuicFLMessages", "QUICFL_quantize", "quicfl_compress", "quicfl_decompress",
     "quicfl_decompress_messages", "quicfl_quantize", "set_tables_prefix",

@@ -88,6 +88,18 @@ SIGNATURES = {
     "uq_scalar_quantize_f32": (ctypes.c_int, [_p, _p, _i64, _i64, _f32, _p, _p, _p, _p, _p, _sz, _p]),
     # x, out, n, d, px_state, px_seeds, px_state_out, S_out, ws, ws_bytes, stream
     "uq_drive_hadamard_f32": (ctypes.c_int, [_p, _p, _i64, _i64, _p, _p, _p, _p, _p, _sz, _p]),
+    "uq_kashin_padded_dim": (ctypes.c_int, [_i64, ctypes.POINTER(_i64)]),
+    "uq_kashin_workspace_bytes": (ctypes.c_int, [_i64, _i64, ctypes.POINTER(_sz)]),
+    # x, n, dim, D, niters, eta, delta, err, nlevels, signs, sign_row, runs, run_row, run_words, bins, mn, step,
+    # info, iters, ws, ws_bytes, stream
+    "uq_kashin_compress_f32": (ctypes.c_int, [_p, _i64, _i64, _i64, _i32, _f64, _f64, _f64, _i32, _p, _p, _p, _p, _i64,
+                                              _p, _p, _p, _p, _p, _p, _sz, _p]),
+    # bins, mn, step, n, dim, D, signs, sign_row, out, ws, ws_bytes, stream
+    "uq_kashin_decompress_f32": (ctypes.c_int, [_p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _sz, _p]),
+    # x, out, n, dim, D, niters, eta, delta, err, nlevels, signs, sign_row, runs, run_row, run_words, mn, step, info,
+    # iters, ws, ws_bytes, stream
+    "uq_kashin_f32": (ctypes.c_int, [_p, _p, _i64, _i64, _i64, _i32, _f64, _f64, _f64, _i32, _p, _p, _p, _p, _i64, _p, _p,
+                                     _p, _p, _p, _sz, _p]),
     "uq_tc_bound":(ctypes.c_int, [_i64, ctypes.POINTER(_sz)]),
     "uq_tc_workspace_bytes": (ctypes.c_int, [_i64, _i64, ctypes.POINTER(_sz)]),
     "uq_tc_encode": (ctypes.c_int, [_p, _p, _i64, _i64, _i64, _i32, _p, _sz, _p, _p, _sz, _p]),

@@ -373,6 +373,13 @@ int uq_internal::rht_inverse(float* rot, float* out, int64_t n, int64_t D, int64
     return launch_passes(P, fwht_args(rot, signs, sign_row, nullptr, nullptr, D, dim, EdenTables{}), n, rot, out, st);
 }
 
+// AS:123-141 of rows that are a power of two long: QUIC-FL's front without its norm
+int uq_internal::rht_forward_rows(const float* x, float* buf, float* out, int64_t n, int64_t D, const int8_t* signs,
+                                  const int32_t* sign_row, float** result, hipStream_t st) {
+    const EdenPlan& P = record(eden_plan(UQ_EDEN_OP_QFL_FRONT, n, D, 0, 0));
+    return launch_passes(P, fwht_args(x, signs, sign_row, nullptr, nullptr, D, D, EdenTables{}), n, buf, out, st, result);
+}
+
 extern "C" {
 
 int uq_test_eden_plan(int32_t op, int64_t n, int64_t dim, int32_t nbits, int32_t mode, int64_t* plan_out, int32_t cap) {

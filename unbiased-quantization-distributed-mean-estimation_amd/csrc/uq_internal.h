@@ -1,7 +1,7 @@
 // uq_internal.h — host functions and state that cross the library's translation units.
 //
 // Each scheme is one .hip (uq_unbiased.hip, uq_biased.hip, uq_eden.hip, uq_quicfl.hip, uq_rand.hip,
-// uq_codec.hip) beside the host core, uq_core.hip.  What they share on the host is declared
+// uq_kashin.hip, uq_codec.hip) beside the host core, uq_core.hip.  What they share on the host is declared
 // here and defined in exactly one of them, so every piece of state (the error string, the side
 // streams) exists once in the library.  Nothing here is exported: the
 // namespace has hidden visibility.  Signatures use plain types only: the kernels' argument
@@ -104,6 +104,10 @@ int rht_norm_front(const float* x, int64_t n, int64_t dim, const int8_t* signs, 
 // which writes out [n][dim].
 int rht_inverse(float* rot, float* out, int64_t n, int64_t D, int64_t dim, const int8_t* signs,
                 const int32_t* sign_row, hipStream_t st);
+// The sender's RHT of rows that are D = 2^p long already (Kashin's padded residual, AS:222-224): the
+// passes alternate between buf and out [n][D] each, x is only read; *result = the one holding the result.
+int rht_forward_rows(const float* x, float* buf, float* out, int64_t n, int64_t D, const int8_t* signs,
+                     const int32_t* sign_row, float** result, hipStream_t st);
 
 }  // namespace uq_internal
 

@@ -20,9 +20,11 @@ Type_biased_quantize (ND:139-140, no draws), QUICFL_quantize (ND:141-142: one ra
 for the message seed, then D words of the same generator for bernoulli(p_X), AS:489 -- the host
 advances a copy of the CPU generator past those words and hands each message its generator
 state, so the batched sender draws exactly the reference's words; tables from `quicfl=(sender,
-receiver)` or the drop-in's prefix).  Kashin is not built, and DRIVE and Scalar (rand_schemes.py:
-drop-ins and px_states batch forms) are not wired into this loop, so the draw stream equals that
-of a driver calling only the selected schemes.
+receiver)` or the drop-in's prefix), Kashin_quantize (ND:143-144, one randint(0, 100) per call:
+the stochastic quantizer's seed, AS:841; a client the reference's torch.bernoulli raises on raises
+RuntimeError here).  DRIVE and Scalar (rand_schemes.py: drop-ins and px_states batch forms) are
+not wired into this loop, so the draw stream equals that of a driver calling only the selected
+schemes.
 """
 from __future__ import annotations
 
@@ -40,10 +42,11 @@ from . import _lib
 from ._mtstate import advance_generator, generator_words, set_generator_words
 from .biased import biased_quantize
 from .eden import eden_compress, eden_decompress, eden_quantize, padded_dim
+from .kashin import kashin_quantize
 from .quantizer import client_mean, quantize_dequantize
 from .quicfl import _dropin_pair, quicfl_quantize
 
-SCHEME_ORDER = ("eden", "unbiased", "biased", "quicfl")     # ND:135-142 call order
+SCHEME_ORDER = ("eden", "unbiased", "biased", "quicfl", "kashin")     # ND:135-144 call order
 
 __all__ = ["DISTRIBUTIONS", "draw_vectors", "legacy_draw", "nmse_simulation", "Suspended", "USERS_ND"]
 
@@ -248,8 +251,8 @@ def _client_draws(gen, n, order, rates, qD):
     for _ in range(n):
         for sc in order:
             for r in rates:
-                if sc == "eden":
-                    draws[(sc, r)].append(int(torch.randint(0, 100, (1,), generator=gen)))   # AS:797
+                if sc == "eden" or sc == "kashin":
+                    draws[(sc, r)].append(int(torch.randint(0, 100, (1,), generator=gen)))   # AS:797, AS:841
                 elif sc == "unbiased":
                     draws[(sc, r)].append(float(torch.rand(1, generator=gen)))               # AS:634
                 elif sc == "quicfl":
@@ -263,7 +266,7 @@ def _client_words(order, rates, qD):
     """32-bit words of torch's CPU generator one client takes in _client_draws: randint(0, 100)
     and rand(1) one each (ATen's random() for a range below 2^32 / a float), QUIC-FL's seed plus its
     D words."""
-    per = {"eden": 1, "unbiased": 1, "biased": 0, "quicfl": 1 + (qD or 0)}
+    per = {"eden": 1, "unbiased": 1, "biased": 0, "quicfl": 1 + (qD or 0), "kashin": 1}
     return sum(per[sc] for sc in order) * len(rates)
 
 
@@ -375,6 +378,8 @@ def nmse_simulation(dist: str = "normal", dim: int = 2048, users=USERS_ND, num_i
                     states = np.stack([w for _, w in draws[(sc, r)]])
                     q, _, _ = quicfl_quantize(xd, r, seeds, [123] * n, sender=qsend,                 # AS:814-832
                                               recv_table=qrecv.recv_table[r], px_states=states)
+                elif sc == "kashin":
+                    q = kashin_quantize(xd, r, seeds=draws[(sc, r)])    # AS:834-854; raises for a flagged client
                 elif eden_scales is None and eden_scales_out is None:
                     q = eden_quantize(xd, r, seeds=draws[(sc, r)])
                 else:                                 # compress, (record / replace the scale), decompress
