@@ -578,7 +578,9 @@ int uq_drive_hadamard_f32(const float* x, float* out, int64_t n, int64_t d, cons
  *   for i < niters - 1 the residual loses the clamped part's inverse transform and M *= f32(eta);
  *   then err = norm(x - inverse(c)[:dim]) / norm(residual) and the client is done when err <
  *   f32(err).  At i = 0 the two norms are the same bits and at i = niters - 1 the test changes
- *   nothing, so it is evaluated for 0 < i < niters - 1 only.  Every norm is torch's CPU order for
+ *   nothing, so it is evaluated for 0 < i < niters - 1 only.  That needs f32(err) <= 1: the quotient
+ *   at i = 0 is 1.0 or NaN, below a larger bound only, where the reference exits after its first
+ *   transform; f32(err) > 1 is refused with UQ_E_INVALID.  Every norm is torch's CPU order for
  *   one thread.  iters [n] = the forward transforms each client ran.
  * The stochastic quantizer (AS:67-82) of c: mn = min(c), step = (max(c) - mn) / f32(nlevels - 1),
  *   q = (c - mn) / step, bins = floor(q) + bernoulli(q - floor(q)); coordinate k takes word k of a

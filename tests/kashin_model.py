@@ -44,9 +44,23 @@ def inverse_rht(v: np.ndarray, seed: int = ROTATION_SEED) -> np.ndarray:
     return (E.hadamard(v) * _diag(v.shape[0], seed)).astype(f32)
 
 
+@functools.lru_cache(maxsize=4)
+def normal_batch(seed: int, n: int, d: int) -> np.ndarray:
+    """RandomState(seed).normal(size=(n, d)).astype(f32), read-only (shared between tests)."""
+    x = np.random.RandomState(seed).normal(size=(n, d)).astype(f32)
+    x.setflags(write=False)
+    return x
+
+
 def gen_input(c) -> np.ndarray:
-    """A fixture case's input from its spec."""
+    """A fixture case's input from its spec.  "normal" is RandomState(seed).normal(size=d).astype(f32)
+    (golden_data.spec_gen's); "normal_f32" names that draw itself and "normal_row" row c["row"] of
+    RandomState(seed).normal(size=(c["n"], d)).astype(f32) (tests/golden/kashin_edges.*)."""
     d, kind = c["d"], c["dist"]
+    if kind == "normal_f32":
+        return np.random.RandomState(c["seed"]).normal(size=d).astype(f32)
+    if kind == "normal_row":
+        return normal_batch(c["seed"], c["n"], d)[c["row"]].copy()
     if kind == "onehot":
         v = np.zeros(d, f32)
         v[c["seed"] % d] = f32(2.5)
@@ -60,6 +74,31 @@ def gen_input(c) -> np.ndarray:
         v[d // 3] = np.nan if kind == "nan" else np.inf
         return v
     return G.spec_gen(c)
+
+
+def sample_positions(k: int, d: int, count: int = 4096) -> np.ndarray:
+    """The positions at which tests/golden/kashin_edges.* keeps case k's long output."""
+    return np.sort(np.random.RandomState(k).choice(d, count, replace=False))
+
+
+def edge_fixture():
+    """(cases, npz) of tests/golden/kashin_edges.* (make_golden_kashin_edges.py)."""
+    import json
+    import os
+    cases = json.load(open(os.path.join(G.GOLDEN, "kashin_edges.json")))["cases"]
+    return cases, np.load(os.path.join(G.GOLDEN, "kashin_edges.npz"))
+
+
+def edge_expected(c, Z) -> dict:
+    """A kashin_edges case's recorded results: ms = (min, step) and either out and bins (u16) in
+    full or out_s at sample_positions with the sha256s in the case (`same_as` followed)."""
+    k = c.get("same_as", c["idx"])
+    e = {"ms": Z[f"ms{k}"]}
+    if f"out{k}" in Z.files:
+        e["out"], e["bins"] = Z[f"out{k}"], Z[f"bins{k}"]
+    else:
+        e["out_s"], e["pos"] = Z[f"out{k}_s"], sample_positions(k, c["x"]["d"])
+    return e
 
 
 def kashin(x, bits: int, seed: int, niters: int = 3, eta: float = 0.9, delta: float = 1.0, err: float = 1e-6):

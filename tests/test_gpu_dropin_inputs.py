@@ -1,6 +1,6 @@
-"""GPU: what the six drop-ins do with their input before any kernel runs -- Type_unbiased_quantize,
-Type_biased_quantize, EDEN_quantize_Hadamard, QUICFL_quantize, Scalar_quantize and
-DRIVE_quantize_Hadamard.  The kernels are not under test here, only what reaches them: every
+"""GPU: what the seven drop-ins do with their input before any kernel runs -- Type_unbiased_quantize,
+Type_biased_quantize, EDEN_quantize_Hadamard, QUICFL_quantize, Scalar_quantize,
+DRIVE_quantize_Hadamard and Kashin_quantize.  The kernels are not under test here, only what reaches them: every
 form an input may take gives the bits of the contiguous f32 GPU tensor and leaves torch's
 global CPU generator where that form leaves it; the input is only read; rank-2, empty and
 unknown-rate calls end the way each scheme ends them.
@@ -25,7 +25,8 @@ from quicfl_tables import write_tables  # noqa: E402
 SEED = 7
 DIMS = (33, 2050)
 RANK1_ONLY = ("Type_unbiased_quantize", "Type_biased_quantize", "Scalar_quantize", "DRIVE_quantize_Hadamard")
-FLATTENING = ("EDEN_quantize_Hadamard", "QUICFL_quantize")
+# Kashin_quantize (AS:834-854) takes [1, d] through numel() and broadcasting: the 1-D call's bits and draw on torch CPU
+FLATTENING = ("EDEN_quantize_Hadamard", "QUICFL_quantize", "Kashin_quantize")
 SCHEMES = RANK1_ONLY + FLATTENING
 FORMS = ("list", "numpy_f64", "cpu_f32", "gpu_f64", "gpu_strided", "requires_grad")
 
@@ -166,6 +167,14 @@ def test_empty_input_eden_returns_an_empty_array_after_the_seed_draw(dropins):
     after = state_after(lambda: torch.randint(0, 100, (1,)))                 # AS:797 is still taken
     for v in empty_inputs():
         kind, out, st = call(dropins, "EDEN_quantize_Hadamard", v)
+        assert kind == "numpy" and out.shape == (0,)
+        assert torch.equal(st, after)
+
+
+def test_empty_input_kashin_returns_an_empty_array_after_the_seed_draw(dropins):
+    after = state_after(lambda: torch.randint(0, 100, (1,)))                 # AS:841 is still taken
+    for v in empty_inputs():
+        kind, out, st = call(dropins, "Kashin_quantize", v)
         assert kind == "numpy" and out.shape == (0,)
         assert torch.equal(st, after)
 

@@ -1,5 +1,5 @@
 """Kashin_quantize on the host: the NumPy model (tests/kashin_model.py) against the reference's
-own outputs (tests/golden/kashin_vectors.*), and the host pieces of the GPU path -- the padded
+own outputs (tests/golden/kashin_vectors.* and kashin_edges.*), and the host pieces of the GPU path -- the padded
 dimension, the prng seeds, the run tables, the harness's draws, the C argument checks."""
 import ctypes
 import hashlib
@@ -16,6 +16,7 @@ from tests import kashin_model as M
 from oracle import uq_quicfl as Q
 
 META = json.load(open(os.path.join(G.GOLDEN, "kashin_vectors.json")))["cases"]
+EDGES, _ = M.edge_fixture()
 PADDED = {1: 2, 2: 4, 3: 4, 5: 8, 7: 16, 13: 16, 14: 32, 27: 32, 28: 64, 1740: 2048, 1741: 4096, 2048: 4096,
           3481: 4096, 3482: 8192}
 
@@ -60,6 +61,85 @@ def test_model_equals_reference(c, Z):
         assert hashlib.sha256(bins.tobytes()).hexdigest() == c["bins_sha"]
         assert hashlib.sha256(r["out"].tobytes()).hexdigest() == c["sha"]
         assert G.bits_equal(r["out"][Z[f"out{k}_pos"]], Z[f"out{k}_s"])
+
+
+@pytest.fixture(scope="module")
+def ZE():
+    return M.edge_fixture()[1]
+
+
+def test_edge_fixture_covers_the_issue(ZE):
+    def has(group, d=None, dist="normal", **kw):
+        return any(c["group"] == group and (d is None or c["x"]["d"] == d) and c["x"]["dist"] == dist and
+                   all(c[k] == v for k, v in kw.items()) for c in EDGES)
+    defaults = dict(niters=3, err=1e-6, eta=0.9, delta=1.0)
+    for bits in (3, 5, 6, 7, 8):
+        for d in (13, 1741, 5000):
+            assert has("rates", d, bits=bits, **defaults)
+        assert has("rates", dist="lognormal", bits=bits, **defaults)
+    top = [c for c in EDGES if c["group"] == "top_bin"]
+    assert len(top) == 1 and top[0]["x"] == {"dist": "normal_f32", "d": 2048, "seed": 5238}
+    assert (top[0]["bits"], top[0]["seed"], top[0]["bins_max"]) == (8, 37, 256)
+    tb = M.edge_expected(top[0], ZE)["bins"]
+    assert tb.dtype == np.uint16 and np.flatnonzero(tb == 256).tolist() == [1399] and tb.max() == 256
+    assert all(c["bins_max"] == 2 ** c["bits"] - 1 for c in EDGES if c["group"] != "top_bin")
+    for d in (4, 6, 8, 12, 15, 16, 2047, 2055, 2056, 4100, 4103, 6147, 6150):
+        assert has("norm_edges", d, bits=1, **defaults)
+    for d in (100, 5000):
+        for niters in (1, 2, 4, 5):
+            assert has("niters", d, **dict(defaults, niters=niters))
+        assert has("eta", d, **dict(defaults, eta=0.75))
+        assert has("delta", d, **dict(defaults, delta=0.5)) and has("delta", d, **dict(defaults, delta=2.0))
+    for niters in (4, 5):
+        rows = [c for c in EDGES if c["group"] == "err1" and c["x"]["d"] == 5000 and c["niters"] == niters]
+        assert [c["x"]["row"] for c in rows] == list(range(8))
+        assert all(c["x"] == {"dist": "normal_row", "n": 24, "d": 5000, "seed": 11, "row": c["x"]["row"]} and c["err"] == 1.0
+                   for c in rows)
+        if niters == 4:
+            assert [c["iters"] for c in rows] == [2, 4, 3, 4, 2, 4, 2, 3]
+        assert max(c["iters"] for c in rows) == niters and min(c["iters"] for c in rows) == 2
+    assert all(c["iters"] == c["niters"] for c in EDGES if c["group"] == "niters" and c["niters"] <= 2)
+    assert has("large", 1 << 21, bits=1, **defaults)
+    for c in EDGES:                                      # in full below 8192 coordinates, else sha256s and samples
+        e = M.edge_expected(c, ZE)
+        assert e["ms"].dtype == np.float32 and e["ms"].shape == (2,)
+        if c["x"]["d"] < 8192:
+            assert e["out"].shape == (c["x"]["d"],) and e["bins"].shape == (c["D"],) and e["bins"].dtype == np.uint16
+        else:
+            assert e["out_s"].shape == e["pos"].shape == (4096,) and len(c["sha"]) == len(c["bins_sha"]) == 64
+        assert c["D"] == M.kashin_padded_dim(c["x"]["d"])
+        if "same_as" in c:                               # only a client that left the loop early repeats a result
+            o = EDGES[c["same_as"]]
+            assert o["x"] == c["x"] and (o["bits"], o["seed"], o["err"]) == (c["bits"], c["seed"], c["err"])
+    size = [os.path.getsize(os.path.join(G.GOLDEN, f)) for f in ("kashin_edges.npz", "kashin_vectors.npz")]
+    assert size[0] <= size[1]
+
+
+@pytest.mark.parametrize("c", EDGES, ids=lambda c: f"{c['idx']}-{c['group']}-d{c['x']['d']}-b{c['bits']}")
+def test_model_equals_reference_edges(c, ZE):
+    """The model with the loop's parameters, 8 bits and its bin 256 included, against the reference."""
+    r = M.kashin(M.gen_input(c["x"]), c["bits"], c["seed"], c["niters"], c["eta"], c["delta"], c["err"])
+    e = M.edge_expected(c, ZE)
+    assert not r["raises"]
+    assert r["iters"] == c["iters"]
+    assert G.bits_equal([r["mn"], r["step"]], e["ms"])
+    assert r["bins"].max() == c["bins_max"] and r["bins"].min() >= 0
+    bins = r["bins"].astype(np.uint16)
+    if "out" in e:
+        assert np.array_equal(bins, e["bins"])
+        assert G.bits_equal(r["out"], e["out"])
+    else:
+        assert hashlib.sha256(bins.tobytes()).hexdigest() == c["bins_sha"]
+        assert hashlib.sha256(r["out"].tobytes()).hexdigest() == c["sha"]
+        assert G.bits_equal(r["out"][e["pos"]], e["out_s"])
+
+
+def test_model_exits_after_one_transform_above_err_1():
+    """AS:236 at i = 0 compares 1.0 with the bound: a bound above 1 ends the loop there (the
+    reference with data['err'] = 1.5 does; the library refuses such a bound)."""
+    x = M.gen_input({"dist": "normal", "d": 100, "seed": 3})
+    assert M.kashin(x, 1, 0, niters=4, err=1.5)["iters"] == 1
+    assert M.kashin(x, 1, 0, niters=4, err=1.0)["iters"] >= 2
 
 
 def test_the_seed_drawn_is_one_randint_word():
@@ -144,13 +224,15 @@ def test_c_argument_checks_launch_nothing():
     lib = uqdme.load_library()
     one = ctypes.c_void_p(16)          # non-null, never dereferenced: every call below is refused first
     null = ctypes.c_void_p(0)
+    E_INVALID = -1                     # UQ_E_INVALID
 
-    def compress(n=1, dim=5, D=8, niters=3, nlevels=2, x=one, signs=one, runs=one, run_words=1000, bins=one, ws=one):
-        return lib.uq_kashin_compress_f32(x, n, dim, D, niters, 0.9, 1.0, 1e-6, nlevels, signs, null, runs, null,
+    def compress(n=1, dim=5, D=8, niters=3, nlevels=2, x=one, signs=one, runs=one, run_words=1000, bins=one, ws=one,
+                 err=1e-6):
+        return lib.uq_kashin_compress_f32(x, n, dim, D, niters, 0.9, 1.0, err, nlevels, signs, null, runs, null,
                                           run_words, bins, one, one, one, one, ws, 1 << 40, null)
 
-    def fused(n=1, dim=5, D=8, niters=3, nlevels=2, x=one, out=one, info=one):
-        return lib.uq_kashin_f32(x, out, n, dim, D, niters, 0.9, 1.0, 1e-6, nlevels, one, null, one, null, 1000, null,
+    def fused(n=1, dim=5, D=8, niters=3, nlevels=2, x=one, out=one, info=one, err=1e-6):
+        return lib.uq_kashin_f32(x, out, n, dim, D, niters, 0.9, 1.0, err, nlevels, one, null, one, null, 1000, null,
                                  null, info, null, one, 1 << 40, null)
 
     def decompress(n=1, dim=5, D=8, bins=one, out=one):
@@ -163,6 +245,16 @@ def test_c_argument_checks_launch_nothing():
         assert f(niters=0) != 0
         assert f(nlevels=1) != 0 and f(nlevels=257) != 0
         assert f(n=-1) != 0
+        # f32(err) > 1: the reference leaves the loop after its first transform, the device loop cannot
+        for err in (1.5, 1.0000001, float("inf")):
+            assert f(err=err) == E_INVALID and f(err=err, n=0) == E_INVALID
+            msg = lib.uq_last_error()
+            assert b"err must be <= 1" in msg and b"first transform" in msg
+        # err = 1.0 (and a double that rounds to f32 1.0) passes that check: refused by the next one, or a no-op
+        for err in (1.0, 1.0 + 1e-12):
+            assert f(err=err, n=0) == 0
+            assert f(err=err, D=6) == E_INVALID and b"power of two" in lib.uq_last_error()
+            assert f(err=err, x=null) == E_INVALID and b"null pointer" in lib.uq_last_error()
     assert compress(signs=null) != 0 and compress(runs=null) != 0 and compress(bins=null) != 0
     assert compress(run_words=0) != 0 and compress(ws=null) != 0
     assert fused(out=null) != 0 and fused(info=null) != 0

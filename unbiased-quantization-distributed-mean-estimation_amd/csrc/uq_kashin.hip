@@ -89,6 +89,10 @@ int kashin_check_params(const KashinCall& c, const KashinParams& p) {
     if (p.niters < 1) return fail(UQ_E_INVALID, "kashin: niters must be >= 1");
     if (p.nlevels < 2 || p.nlevels > 256) return fail(UQ_E_INVALID, "kashin: nlevels must be in 2..256");
     if (!(p.delta > 0.0)) return fail(UQ_E_INVALID, "kashin: delta must be > 0");
+    // AS:236 at i = 0 compares 1.0 (or NaN) with the bound; kashin_coefficients skips that test
+    if ((float)p.err > 1.0f)
+        return fail(UQ_E_INVALID, "kashin: err must be <= 1 as f32 (above it the reference exits after the first transform, "
+                                  "a test this loop does not evaluate)");
     if (p.run_words < 1 || p.run_words > kKashinMaxD) return fail(UQ_E_INVALID, "kashin: run_words must be in 1..2^28");
     if (c.n > 0 && c.dim > 0 && c.D >= 2 && c.n * ((c.D + p.run_words - 1) / p.run_words) > kKashinMaxGrid)
         return fail(UQ_E_INVALID, "kashin: too many runs for one call");
@@ -122,7 +126,7 @@ int kashin_coefficients(const KashinCall& k, const KashinParams& p, const float*
         if ((rc = rht_inverse(b, other, n, D, dim, k.signs, k.sign_row, st))) return rc;        // AS:231
         kashin_resid_kernel<<<k.egrid(dim), dim3(kKeT), 0, st>>>(r, other, M, done, (float)p.eta, D, dim);
         if ((rc = launched("kashin_resid_kernel launch"))) return rc;
-        if (i == 0) continue;                    // err is num / num there: 1.0 or NaN, never below the bound
+        if (i == 0) continue;                    // err is num / num there: 1.0 or NaN, never below a bound <= 1 (kashin_check_params)
         // AS:235-237: H(c.clone()) * diag, the two norms side by side in one chain wave, the exit test
         if ((rc = hip_check(hipMemcpyAsync(A, c, (size_t)n * D * sizeof(float), hipMemcpyDeviceToDevice, st), "copy c")))
             return rc;

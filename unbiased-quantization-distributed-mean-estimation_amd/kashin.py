@@ -14,6 +14,11 @@ Batched:
     kashin_compress(x[n, d], bits, seeds[n])   -> KashinMessage(bins u8 [n, D], mn[n], step[n], seeds, nbits, d)
     kashin_decompress(msg)                     -> out[n, d]
     kashin_padded_dim(d)                       -> D (AS:202-210)
+    kashin_quantize and kashin_compress also take niters, eta, delta and err (keyword-only, the
+    reference's 3, 0.9, 1.0 and 1e-6); err > 1 is refused: the reference then leaves the loop after
+    its first transform, by a test the device loop skips.  At 8 bits the reference can emit bin 256
+    (DESIGN.md §4.8): kashin_quantize and the drop-in carry it, a u8 message stores 255 and flags
+    KASHIN_BIN_RANGE.
 
 The loop of AS:212-239 (three forward transforms, the exit test after the second) runs on the
 device without a host wait.  The quantizer's bernoulli stream starts from a generator seeded with
@@ -178,8 +183,11 @@ class KashinMessage:
     iters: torch.Tensor = None      # int32 [n]: forward transforms run
 
 
-def _sender(name, x, bits_per_dimension, seeds, generator, niters, run_words, head, tail):
+def _sender(name, x, bits_per_dimension, seeds, generator, niters, eta, delta, err, run_words, head, tail):
     """uq_kashin_<name>(x, *head, n, d, D, the loop's and the quantizer's arguments, *tail, workspace, stream)."""
+    if np.float32(err) > np.float32(1.0):            # before anything is drawn (uq_kashin_* refuse it as well)
+        raise ValueError("Kashin err must be <= 1 as f32: above it the reference exits after its first transform "
+                         "(AS:236 at i = 0), a test the device loop does not evaluate")
     dev = _runtime.device()
     x = as_batch_f32(x, dev)
     nb = _bits(bits_per_dimension)
@@ -195,8 +203,8 @@ def _sender(name, x, bits_per_dimension, seeds, generator, niters, run_words, he
         runs, run_row = _runs_for(s, D, rw, dev)
         ws = workspace_for("uq_kashin_workspace_bytes", dev, n, D)
         fn = f"uq_kashin_{name}"
-        _lib.check(getattr(_lib.load(), fn)(ptr(x), *map(ptr, outs[:len(head)]), n, d, D, int(niters), ETA, DELTA, ERR,
-                                            2 ** nb, ptr(tab), ptr(rows), ptr(runs), ptr(run_row), rw,
+        _lib.check(getattr(_lib.load(), fn)(ptr(x), *map(ptr, outs[:len(head)]), n, d, D, int(niters), float(eta),
+                                            float(delta), float(err), 2 ** nb, ptr(tab), ptr(rows), ptr(runs), ptr(run_row), rw,
                                             *map(ptr, outs[len(head):]), ptr(ws), ws.numel(), stream_ptr(dev)), fn)
     return x, s, nb, outs
 
@@ -209,14 +217,17 @@ def _i32n(n, d, D, dev):
     return torch.zeros(n, dtype=torch.int32, device=dev)
 
 
-def kashin_compress(x, bits_per_dimension=1, seeds=None, *, generator=None, niters: int = NITERS,
-                    run_words=None) -> KashinMessage:
+def kashin_compress(x, bits_per_dimension=1, seeds=None, *, generator=None, niters: int = NITERS, eta: float = ETA,
+                    delta: float = DELTA, err: float = ERR, run_words=None) -> KashinMessage:
     """KashinStochasticQuantizationSender.compress (AS:249-261) for every row of x [n, d].  Nothing
-    waits for the GPU: msg.info flags the rows the reference raises on."""
+    waits for the GPU: msg.info flags the rows the reference raises on.  eta and delta are the
+    sender's constructor arguments (AS:245), niters and err its data['niters'] and data['err'];
+    err > 1 raises ValueError."""
     def bins(n, d, D, dev):
         return torch.empty((n, D), dtype=torch.uint8, device=dev)
     x, s, nb, (b, mn, step, info, iters) = _sender("compress_f32", x, bits_per_dimension, seeds, generator, niters,
-                                                   run_words, (), (bins, _f32n, _f32n, _i32n, _i32n))
+                                                   eta, delta, err, run_words, (),
+                                                   (bins, _f32n, _f32n, _i32n, _i32n))
     return KashinMessage(bins=b, mn=mn, step=step, seeds=s, nbits=nb, dim=x.shape[1], info=info, iters=iters)
 
 
@@ -246,19 +257,20 @@ def _raise_flagged(info) -> None:
                            (f" and {bad.size - 1} more" if bad.size > 1 else ""))
 
 
-def kashin_quantize(x, bits_per_dimension=1, seeds=None, *, generator=None, niters: int = NITERS, run_words=None,
-                    return_info: bool = False):
+def kashin_quantize(x, bits_per_dimension=1, seeds=None, *, generator=None, niters: int = NITERS, eta: float = ETA,
+                    delta: float = DELTA, err: float = ERR, run_words=None, return_info: bool = False):
     """Kashin_quantize for every row of x [n, d] (quantizer seed per row; seeds=None draws them as n
     successive AS:841 draws from `generator` or the global one).  return_info: (out, info [n]
     int32, iters [n] int32) on the device without waiting for the GPU; else out, after a check
-    of info that raises RuntimeError for a row the reference raises on."""
+    of info that raises RuntimeError for a row the reference raises on.  niters, eta, delta and
+    err as in kashin_compress."""
     def out(n, d, D, dev):
         return torch.empty((n, d), dtype=torch.float32, device=dev)
 
     def none(n, d, D, dev):
         return None
-    _, _, _, (q, _, _, info, iters) = _sender("f32", x, bits_per_dimension, seeds, generator, niters, run_words, (out,),
-                                             (none, none, _i32n, _i32n))
+    _, _, _, (q, _, _, info, iters) = _sender("f32", x, bits_per_dimension, seeds, generator, niters, eta, delta, err,
+                                             run_words, (out,), (none, none, _i32n, _i32n))
     if return_info:
         return q, info, iters
     _raise_flagged(info)
