@@ -151,13 +151,17 @@ int uq_test_last_biased_plan(int64_t* plan_out, int32_t cap);
  *   workgroups per client (grid x; grid y is n)
  *   [22] the forward RHT copies its result from the workspace into out   [23] tables per client
  *   of the segmented norm (0 where the shape has no segmented region)
+ *   [24] 1 for a fractional rate (the uq_eden_*_frac_f32 entry points): the forms above name the
+ *   mask-aware instances of KE4 / KE4s and of the receiver's first pass
  * uq_test_eden_plan: host only, launches nothing: the plan of op (UQ_EDEN_OP_*) for n clients of
- * dim coordinates; nbits matters to compress (1 or 2), mode (uq_eden_norm_f32's) to the norm op,
+ * dim coordinates; nbits matters to compress and decompress (1, 2, or UQ_EDEN_NBITS_FRAC for
+ * 1 < nbits < 2, which takes the rows of 2 bits), mode (uq_eden_norm_f32's) to the norm op,
  * whose norm form is 0 when mode 2 is asked for a shape the segmented norm does not take.  No
  * forms and no passes for n == 0 or dim == 0.
  * uq_test_last_eden_plan: the plan of this thread's last call of that op (no passes and no forms
  * when it launched nothing); a uq_eden_f32 call records a compress and a decompress plan. */
-#define UQ_EDEN_PLAN_FIELDS 24
+#define UQ_EDEN_PLAN_FIELDS 25
+#define UQ_EDEN_NBITS_FRAC 12           /* the plan hook's nbits for a fractional rate, 1 < nbits < 2 */
 #define UQ_EDEN_MAX_PASSES 4            /* three up to D = 2^28 (12 + 8 + 8), the quantizers' limit */
 #define UQ_EDEN_OP_COMPRESS 0
 #define UQ_EDEN_OP_DECOMPRESS 1
@@ -393,8 +397,8 @@ int uq_type_biased_f32(const float* x, float* out, int64_t n, int64_t d, int64_t
  * uq_eden_compress_f32: bins [n][D] u8 and scale [n] f32 of EdenSender.compress for integer
  *   nbits (1 or 2, the tables the reference defines); client j uses diagonal row
  *   sign_row[j] (device int32 [n]).  Rotation, norm (torch CPU order) and bins are
- *   bit-identical to the reference; scale's dot product is accumulated in fp64 (the
- *   reference's MKL sdot order is CPU-dependent): scale within 1e-6 relative.
+ *   bit-identical to the reference, and so is the scale: its torch.dot is summed in MKL sdot's
+ *   order on the fixtures' host (oracle/uq_eden.py torch_dot).
  * uq_eden_decompress_f32: out [n][dim] = scale * RHT^-1(centroids[bins])[:dim].
  * uq_eden_f32: both (EDEN_quantize_Hadamard for a batch); scale_out [n] or NULL.
  * Workspace: uq_eden_workspace_bytes. */
@@ -524,6 +528,32 @@ int uq_eden_decompress_f32_sb(const uint8_t* bins, const float* scale, int64_t n
 int uq_eden_f32_sb(const float* x, float* out, int64_t n, int64_t dim, int32_t nbits, const int8_t* signs,
                    const int32_t* sign_row, const uint32_t* sign_bits, float* scale_out, void* ws, size_t ws_bytes,
                    void* stream);
+/* Fractional rates 1 < nbits < 2 (EdenSender.stochastic_quantize, AS:352-368; the receiver,
+ * AS:401-411), bit-identical to the reference: p_high = nbits - 1, and coordinate k of the padded
+ * row takes the 2-bit table where mask[k] = torch.bernoulli(p_high) of a CPU generator seeded with
+ * 7 * seed + 13 is set, the 1-bit table elsewhere; bins and centroids are mixed accordingly and the
+ * scale is f32(nrm * nrm) / torch.dot(mixed centroids, vec) in the same order as above.
+ * uq_eden_mask_bits: the mask rows, bits [rows][ceil(D / 32)] u32 in uq_rht_sign_bits's layout: bit
+ *   i % 32 of word i / 32 of row r set where word i of MT19937 seeded with the low 32 bits of
+ *   7 * seeds[r] + 13 (seeds: device int64 [rows], the ROTATION seeds; 64-bit arithmetic) has
+ *   low24(w) < threshold, threshold = ceil(f32(p_high) * 2^24) <= 2^24 -- the draw f32(low24) * 2^-24
+ *   < f32(p_high).  A pure function of (seed, D, threshold): callers cache the rows.
+ * uq_eden_compress_frac_f32 / uq_eden_decompress_frac_f32 / uq_eden_frac_f32: the three _sb entry
+ *   points for such a rate: no nbits; client j reads mask row mask_row[j] (device int32 [n], or
+ *   NULL: row 0) of mask_bits.  bins are 0..3 where the mask is set and 0..1 elsewhere; of a
+ *   message with another bin the receiver reads the bin's low two bits (its low bit where the mask
+ *   is clear), where the reference's torch.take raises.  Dispatch, workspace (uq_eden_workspace_bytes) and every other argument as
+ *   for nbits = 2. */
+int uq_eden_mask_bits(const int64_t* seeds, int64_t rows, int64_t D, uint32_t threshold, uint32_t* bits, void* stream);
+int uq_eden_compress_frac_f32(const float* x, int64_t n, int64_t dim, const int8_t* signs, const int32_t* sign_row,
+                              const uint32_t* sign_bits, const uint32_t* mask_bits, const int32_t* mask_row, uint8_t* bins,
+                              float* scale, void* ws, size_t ws_bytes, void* stream);
+int uq_eden_decompress_frac_f32(const uint8_t* bins, const float* scale, int64_t n, int64_t dim, const int8_t* signs,
+                                const int32_t* sign_row, const uint32_t* sign_bits, const uint32_t* mask_bits,
+                                const int32_t* mask_row, float* out, void* ws, size_t ws_bytes, void* stream);
+int uq_eden_frac_f32(const float* x, float* out, int64_t n, int64_t dim, const int8_t* signs, const int32_t* sign_row,
+                     const uint32_t* sign_bits, const uint32_t* mask_bits, const int32_t* mask_row, float* scale_out,
+                     void* ws, size_t ws_bytes, void* stream);
 /* torch.norm(v[j], 2) of each row of v [n][D] f32 in torch's CPU order (AS:329: 8 lanes of
  * fma chains, lanes added in order, sqrt), the norm the EDEN entry points use:
  *   mode 1: the sequential chains (one chain per torch lane; what batches above 256 rows use)

@@ -80,6 +80,11 @@ SIGNATURES = {
     "uq_eden_compress_f32_sb": (ctypes.c_int, [_p, _i64, _i64, _i32, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "uq_eden_decompress_f32_sb": (ctypes.c_int, [_p, _p, _i64, _i64, _i32, _p, _p, _p, _p, _p, _sz, _p]),
     "uq_eden_f32_sb": (ctypes.c_int, [_p, _p, _i64, _i64, _i32, _p, _p, _p, _p, _p, _sz, _p]),
+    "uq_eden_mask_bits": (ctypes.c_int, [_p, _i64, _i64, ctypes.c_uint32, _p, _p]),
+    # (x | bins, scale | x, out), n, dim, signs, sign_row, sign_bits, mask_bits, mask_row, outputs, ws, ws_bytes, stream
+    "uq_eden_compress_frac_f32": (ctypes.c_int, [_p, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "uq_eden_decompress_frac_f32": (ctypes.c_int, [_p, _p, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "uq_eden_frac_f32": (ctypes.c_int, [_p, _p, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "uq_eden_norm_workspace_bytes": (ctypes.c_int, [_i64, _i64, ctypes.POINTER(_sz)]),
     "uq_eden_norm_f32": (ctypes.c_int, [_p, _i64, _i64, _i32, _p, _p, _sz, _p]),
     "uq_rand_workspace_bytes": (ctypes.c_int, [_i64, _i64, ctypes.POINTER(_sz)]),

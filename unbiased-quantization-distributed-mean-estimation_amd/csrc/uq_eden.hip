@@ -60,6 +60,7 @@ struct EdenPlan {
     int32_t first_bits = 0, npass = 0;
     EdenPass pass[UQ_EDEN_MAX_PASSES] = {};
     bool copy_back = false;   // forward RHT: the last pass wrote the workspace, not out
+    bool frac = false;        // a fractional rate: the mask-aware dot kernels / first receiver pass
     bool sender() const { return op == UQ_EDEN_OP_COMPRESS || op == UQ_EDEN_OP_RHT_FORWARD || op == UQ_EDEN_OP_QFL_FRONT; }
     // MODE of the first pass: 1 sender (pad, * diag), 2 EDEN's receiver (centroids), 0 plain
     int mode0() const { return sender() ? 1 : op == UQ_EDEN_OP_DECOMPRESS ? 2 : 0; }
@@ -74,6 +75,10 @@ EdenPlan eden_plan(int op, int64_t n, int64_t dim, int32_t nbits, int32_t mode) 
     P.seg = n >= 1 && n <= kSegNormMaxN && D >= kSegMinD && (D & (D - 1)) == 0;
     P.tab_cap = P.seg ? seg_tab_cap(D) : 0;
     if (n < 1 || dim < 1) return P;
+    // a fractional rate takes the rows of 2 bits (never KE2+4, which needs the one boundary at 0
+    // for every coordinate), with the mask-aware instances of the dot kernels and of the
+    // receiver's first pass
+    P.frac = nbits == UQ_EDEN_NBITS_FRAC && (op == UQ_EDEN_OP_COMPRESS || op == UQ_EDEN_OP_DECOMPRESS);
     if (op == UQ_EDEN_OP_COMPRESS && !P.seg && nbits == 1 && D % kNormChunk == 0) {
         // 1 bit, many clients: the norm, the bins and the dot in one read (KE2+4), then KE4 for
         // the clients it flags (a norm that is not positive and finite, an underflowing quotient)
@@ -178,11 +183,24 @@ int launch_norm(const EdenPlan& P, const float* v, int64_t n, char* region, floa
 // KE4s (few clients): the bins and the dot's 64 chains in segments, in the segmented norm's
 // region; the same bits as eden_dotbins_kernel
 int launch_eden_dotseg(const EdenPlan& P, const float* v, int64_t n, float sqrtD, const float* nrm, const EdenTables& tab,
-                       uint8_t* bins, float* scale, char* region, hipStream_t st) {
+                       const EdenMask& m, uint8_t* bins, float* scale, char* region, hipStream_t st) {
     const SegRegion s = seg_region((uintptr_t)region, n, P);
     const int64_t D = P.D, K = D / kEdenTile;
     const int cap = P.tab_cap;
     hipLaunchKernelGGL(eden_thresh_kernel, dim3((unsigned)n), dim3(64), 0, st, nrm, tab, s.thr4);
+    if (P.frac) {       // the same chain of kernels, each element's table by the mask rows
+        hipLaunchKernelGGL(eden_dseg_sum_frac_kernel, dim3((unsigned)K, (unsigned)n), dim3(256), 0, st, v, D, sqrtD, nrm,
+                           s.thr4, tab, bins, s.segsum, m);
+        hipLaunchKernelGGL(eden_segscan_l_kernel<64>, dim3(64u, (unsigned)n), dim3(256), 0, st, s.segsum, K, s.g, s.cnt);
+        hipLaunchKernelGGL(eden_dseg_chain_frac_kernel, dim3((unsigned)(K / kDSegTiles), (unsigned)n), dim3(256), 0, st, v, D,
+                           sqrtD, nrm, s.thr4, tab, s.g, s.e, s.kind, s.cnt, s.tseg, cap, m);
+        hipLaunchKernelGGL(eden_dseg_tab_frac_kernel, dim3((unsigned)cap, (unsigned)n), dim3(256), 0, st, v, D, sqrtD, nrm,
+                           s.thr4, tab, s.g, s.cnt, s.tseg, s.tab, cap, m);
+        hipLaunchKernelGGL(eden_dseg_walk_frac_kernel, dim3(8u, (unsigned)n), dim3(512), 0, st, v, D, sqrtD, nrm, s.thr4, tab,
+                           s.g, s.e, s.kind, s.tab, s.acc64, cap, m);
+        hipLaunchKernelGGL(eden_dseg_final_kernel, dim3((unsigned)n), dim3(64), 0, st, s.acc64, nrm, scale);
+        return launched("eden segmented dot launch");
+    }
     hipLaunchKernelGGL(eden_dseg_sum_kernel, dim3((unsigned)K, (unsigned)n), dim3(256), 0, st, v, D, sqrtD, nrm, s.thr4, tab,
                        bins, s.segsum);
     hipLaunchKernelGGL(eden_segscan_l_kernel<64>, dim3(64u, (unsigned)n), dim3(256), 0, st, s.segsum, K, s.g, s.cnt);
@@ -199,9 +217,11 @@ int launch_eden_dotseg(const EdenPlan& P, const float* v, int64_t n, float sqrtD
 // AS:329-335: the bins and the scale's dot in MKL sdot's order (KE4), scale = f32(nrm * nrm) / dot.  (Ahead of the
 // FWHT launches: kernels are emitted in the order they are named, which tools/kernel_table.py's hashes see.)
 int launch_eden_dotbins(const float* v, int64_t n, int64_t D, float sqrtD, const float* nrm, const EdenTables& tab,
-                        uint8_t* bins, float* scale, hipStream_t st, const int32_t* redo) {
+                        uint8_t* bins, float* scale, hipStream_t st, const int32_t* redo, const EdenMask* frac = nullptr) {
     const dim3 grid((unsigned)((n + kDotWaves - 1) / kDotWaves)), block(64 * kDotWaves);
-    if (tab.nb == 1)
+    if (frac)
+        hipLaunchKernelGGL(eden_dotbins_frac_kernel, grid, block, 0, st, v, D, sqrtD, nrm, tab, bins, scale, n, *frac);
+    else if (tab.nb == 1)
         hipLaunchKernelGGL(eden_dotbins_kernel<1>, grid, block, 0, st, v, D, sqrtD, nrm, tab, bins, scale, n, redo);
     else
         hipLaunchKernelGGL(eden_dotbins_kernel<3>, grid, block, 0, st, v, D, sqrtD, nrm, tab, bins, scale, n, redo);
@@ -236,7 +256,8 @@ FwhtArgs fwht_args(const void* in, const int8_t* signs, const int32_t* sign_row,
 // vectors): in place in `buf`, the last pass into `out`.  Senders: the passes alternate between
 // `buf` and `out` (out == buf: in place; the forward RHT passes its output so that a two-pass
 // transform needs no copy); *result = the buffer holding the result.
-int launch_passes(const EdenPlan& P, FwhtArgs a, int64_t n, float* buf, float* out, hipStream_t st, float** result = nullptr) {
+int launch_passes(const EdenPlan& P, FwhtArgs a, int64_t n, float* buf, float* out, hipStream_t st, float** result = nullptr,
+                  const EdenMask* frac = nullptr) {
     float* dst = nullptr;
     for (int i = 0; i < P.npass; ++i) {
         const EdenPass& s = P.pass[i];
@@ -244,6 +265,19 @@ int launch_passes(const EdenPlan& P, FwhtArgs a, int64_t n, float* buf, float* o
         if (i) a.in = dst;
         a.out = dst = P.sender() ? (i % 2 ? out : buf) : (last ? out : buf);
         const dim3 grid(s.gx, (unsigned)n);
+        if (i == 0 && frac && P.mode0() == 2) {
+            // a fractional receiver's first pass: the plan's kernel for MODE 2, its MODE 3 instance
+            // (the table of each bin by the mask rows); never a later pass's kernel
+            if (s.kernel == UQ_EDEN_PASS_LOW16K) hipLaunchKernelGGL(fwht_low16k_frac_kernel, grid, dim3(1024), 0, st, a, *frac);
+            else if (s.kernel == UQ_EDEN_PASS_LOW4096 && last)
+                hipLaunchKernelGGL((fwht_low4096_frac_kernel<true, true>), grid, dim3(256), 0, st, a, *frac);
+            else if (s.kernel == UQ_EDEN_PASS_LOW4096)
+                hipLaunchKernelGGL((fwht_low4096_frac_kernel<false, false>), grid, dim3(256), 0, st, a, *frac);
+            else if (last) hipLaunchKernelGGL((fwht_pass_frac_kernel<true, true>), grid, dim3(kFwhtT), 0, st, a, s.lo, s.k, *frac);
+            else hipLaunchKernelGGL((fwht_pass_frac_kernel<false, false>), grid, dim3(kFwhtT), 0, st, a, s.lo, s.k, *frac);
+            if (const int rc = launched("fwht_pass_frac_kernel launch")) return rc;
+            continue;
+        }
         select_pass(i ? 0 : P.mode0(), last, last && !P.sender(), [&](auto M, auto L, auto R) {
             constexpr bool l = decltype(L)::value, r = decltype(R)::value;
             switch (s.kernel) {
@@ -277,6 +311,8 @@ struct EdenCall {
     EdenTables tab;
     EdenPlan P;
     EdenLayout w;
+    bool frac = false;        // the _frac entry points: the 2-bit tables, the table per coordinate by `mask`
+    EdenMask mask{};
     char* at(size_t off) const { return (char*)ws + off; }
 };
 
@@ -300,9 +336,10 @@ int eden_call(EdenCall& c, int op, bool null_ptr, F&& body) {
     if (c.dim > ((int64_t)1 << 28)) return fail(UQ_E_INVALID, "dim must be <= 2^28");
     if (!eden_tables(c.nbits, &c.tab)) return fail(UQ_E_INVALID, "EDEN nbits must be 1 or 2 (the reference's tables)");
     if (c.n > 0 && c.dim > 0 && !c.signs) return fail(UQ_E_INVALID, "null signs");
+    if (c.n > 0 && c.dim > 0 && c.frac && !c.mask.bits) return fail(UQ_E_INVALID, "null mask_bits");
     if (c.n == 0 || c.dim == 0) return UQ_OK;
     if (null_ptr) return fail(UQ_E_INVALID, "null pointer");
-    c.P = eden_plan(op, c.n, c.dim, c.nbits, 0);
+    c.P = eden_plan(op, c.n, c.dim, c.frac ? UQ_EDEN_NBITS_FRAC : c.nbits, 0);
     c.w = eden_layout(c.n, c.P);
     if (!c.ws || c.ws_bytes < c.w.total) return fail(UQ_E_WORKSPACE, "workspace too small");
     return body();
@@ -318,7 +355,7 @@ int eden_compress(const EdenCall& c, const float* x, uint8_t* bins, float* scale
     float* nrm = (float*)c.at(c.w.nrm_off);
     const float sqrtD = (float)std::sqrt((double)P.D);
     if (P.dot == UQ_EDEN_DOT_SEGMENTED)
-        return launch_eden_dotseg(P, rot, c.n, sqrtD, nrm, c.tab, bins, scale, c.at(c.w.seg_off), st);
+        return launch_eden_dotseg(P, rot, c.n, sqrtD, nrm, c.tab, c.mask, bins, scale, c.at(c.w.seg_off), st);
     int32_t* redo = nullptr;
     if (P.dot == UQ_EDEN_DOT_FUSED_REDO) {
         redo = (int32_t*)c.at(c.w.redo_off);
@@ -326,13 +363,39 @@ int eden_compress(const EdenCall& c, const float* x, uint8_t* bins, float* scale
                            0, st, rot, c.n, P.D, sqrtD, c.tab, nrm, bins, scale, redo);
         if ((rc = launched("eden_normdot1_kernel launch"))) return rc;
     }
-    return launch_eden_dotbins(rot, c.n, P.D, sqrtD, nrm, c.tab, bins, scale, st, redo);
+    return launch_eden_dotbins(rot, c.n, P.D, sqrtD, nrm, c.tab, bins, scale, st, redo, P.frac ? &c.mask : nullptr);
 }
 
 // EdenReceiver.decompress (AS:378-413)
 int eden_decompress(const EdenCall& c, const uint8_t* bins, const float* scale, float* out) {
     const FwhtArgs a = fwht_args(bins, c.signs, c.sign_row, c.sbits, scale, c.P.D, c.dim, c.tab);
-    return launch_passes(record(c.P), a, c.n, (float*)c.at(c.w.vec_off), out, (hipStream_t)c.stream);
+    return launch_passes(record(c.P), a, c.n, (float*)c.at(c.w.vec_off), out, (hipStream_t)c.stream, nullptr,
+                         c.P.frac ? &c.mask : nullptr);
+}
+
+// The _frac entry points' call: the 2-bit tables, the 1-bit centroids beside the mask rows
+EdenCall frac_call(int64_t n, int64_t dim, const int8_t* signs, const int32_t* sign_row, const uint32_t* sign_bits,
+                   const uint32_t* mask_bits, const int32_t* mask_row, void* ws, size_t ws_bytes, void* stream) {
+    EdenCall c{n, dim, 2, signs, sign_row, sign_bits, ws, ws_bytes, stream};
+    EdenTables one;
+    eden_tables(1, &one);
+    c.frac = true;
+    c.mask = EdenMask{mask_bits, mask_row, one.c[0], one.c[1]};
+    return c;
+}
+
+// compress then decompress on the workspace's bins (uq_eden_f32_sb and its fractional form)
+int eden_fused(EdenCall& c, const float* x, float* out, float* scale_out) {
+    t_last_plan[UQ_EDEN_OP_DECOMPRESS] = EdenPlan{};
+    return eden_call(c, UQ_EDEN_OP_COMPRESS, !x, [&] {
+        uint8_t* bins = (uint8_t*)c.at(c.w.bins_off);
+        float* scale = scale_out ? scale_out : (float*)c.at(c.w.scale_off);
+        const int rc = eden_compress(c, x, bins, scale);
+        if (rc) return rc;
+        if (!out) return fail(UQ_E_INVALID, "null pointer");       // (the receiver's own check, in its place after the sender)
+        c.P = eden_plan(UQ_EDEN_OP_DECOMPRESS, c.n, c.dim, c.frac ? UQ_EDEN_NBITS_FRAC : c.nbits, 0);
+        return eden_decompress(c, bins, scale, out);
+    });
 }
 
 int export_plan(const EdenPlan& P, int64_t* out, int32_t cap) {
@@ -345,6 +408,7 @@ int export_plan(const EdenPlan& P, int64_t* out, int32_t cap) {
     }
     f[22] = P.copy_back;
     f[23] = P.tab_cap;
+    f[24] = P.frac;
     std::copy(f, f + std::min<int32_t>(cap, UQ_EDEN_PLAN_FIELDS), out);
     return UQ_OK;
 }
@@ -487,16 +551,40 @@ int uq_eden_f32_sb(const float* x, float* out, int64_t n, int64_t dim, int32_t n
     // compress (RHT, norm, bins + the MKL-order dot) then decompress: the receiver's first
     // pass reads the 1-byte bins KE4 wrote instead of the 4-byte rotated vector
     EdenCall c{n, dim, nbits, signs, sign_row, sign_bits, ws, ws_bytes, stream};
-    t_last_plan[UQ_EDEN_OP_DECOMPRESS] = EdenPlan{};
-    return eden_call(c, UQ_EDEN_OP_COMPRESS, !x, [&] {
-        uint8_t* bins = (uint8_t*)c.at(c.w.bins_off);
-        float* scale = scale_out ? scale_out : (float*)c.at(c.w.scale_off);
-        const int rc = eden_compress(c, x, bins, scale);
-        if (rc) return rc;
-        if (!out) return fail(UQ_E_INVALID, "null pointer");       // (the receiver's own check, in its place after the sender)
-        c.P = eden_plan(UQ_EDEN_OP_DECOMPRESS, n, dim, nbits, 0);
-        return eden_decompress(c, bins, scale, out);
-    });
+    return eden_fused(c, x, out, scale_out);
+}
+
+// ---- fractional rates 1 < nbits < 2 (AS:352-368, AS:401-411) -----------------------------
+int uq_eden_mask_bits(const int64_t* seeds, int64_t rows, int64_t D, uint32_t threshold, uint32_t* bits, void* stream) {
+    if (rows < 0 || D < 0) return fail(UQ_E_INVALID, "rows and D must be >= 0");
+    if (threshold > (1u << 24)) return fail(UQ_E_INVALID, "threshold must be <= 2^24 (ceil(p_high * 2^24), p_high <= 1)");
+    if (rows == 0 || D == 0) return UQ_OK;
+    if (rows > 65535) return fail(UQ_E_INVALID, "at most 65535 rows per call");
+    if (!seeds || !bits) return fail(UQ_E_INVALID, "null pointer");
+    hipLaunchKernelGGL(eden_mask_bits_kernel, dim3((unsigned)rows), dim3(640), 0, (hipStream_t)stream, seeds, D, threshold,
+                       bits);
+    return launched("eden_mask_bits_kernel launch");
+}
+
+int uq_eden_compress_frac_f32(const float* x, int64_t n, int64_t dim, const int8_t* signs, const int32_t* sign_row,
+                              const uint32_t* sign_bits, const uint32_t* mask_bits, const int32_t* mask_row, uint8_t* bins,
+                              float* scale, void* ws, size_t ws_bytes, void* stream) {
+    EdenCall c = frac_call(n, dim, signs, sign_row, sign_bits, mask_bits, mask_row, ws, ws_bytes, stream);
+    return eden_call(c, UQ_EDEN_OP_COMPRESS, !x || !bins || !scale, [&] { return eden_compress(c, x, bins, scale); });
+}
+
+int uq_eden_decompress_frac_f32(const uint8_t* bins, const float* scale, int64_t n, int64_t dim, const int8_t* signs,
+                                const int32_t* sign_row, const uint32_t* sign_bits, const uint32_t* mask_bits,
+                                const int32_t* mask_row, float* out, void* ws, size_t ws_bytes, void* stream) {
+    EdenCall c = frac_call(n, dim, signs, sign_row, sign_bits, mask_bits, mask_row, ws, ws_bytes, stream);
+    return eden_call(c, UQ_EDEN_OP_DECOMPRESS, !bins || !scale || !out, [&] { return eden_decompress(c, bins, scale, out); });
+}
+
+int uq_eden_frac_f32(const float* x, float* out, int64_t n, int64_t dim, const int8_t* signs, const int32_t* sign_row,
+                     const uint32_t* sign_bits, const uint32_t* mask_bits, const int32_t* mask_row, float* scale_out,
+                     void* ws, size_t ws_bytes, void* stream) {
+    EdenCall c = frac_call(n, dim, signs, sign_row, sign_bits, mask_bits, mask_row, ws, ws_bytes, stream);
+    return eden_fused(c, x, out, scale_out);
 }
 
 int uq_eden_compress_f32(const float* x, int64_t n, int64_t dim, int32_t nbits, const int8_t* signs,

@@ -13,6 +13,7 @@
 //   AS:378-413  EdenReceiver: scale * RHT^-1(centroids[bins])[:dim]
 // Kernels:
 //   KE0 rht_signs_kernel   MT19937 per seed -> int8 diagonal rows (cached by the caller)
+//   KE0m eden_mask_bits_kernel  the mask rows of the fractional rates (AS:360-361), packed bits
 //   KE1 fwht_pass_kernel   up to 12 (first pass) / 8 (later passes) butterfly stages in
 //                          LDS; the first pass fuses pad * diag (sender) or the centroid
 //                          lookup (receiver), the last pass / sqrt(D) (and * diag * scale,
@@ -68,6 +69,39 @@ __device__ __forceinline__ float eden_cent(const EdenCents& t, int b) {
                    m3 = 0u - (uint32_t)(b == 3);
     return __uint_as_float((__float_as_uint(t.c0) & m0) | (__float_as_uint(t.c1) & m1) |
                            (__float_as_uint(t.c2) & m2) | (__float_as_uint(t.c3) & m3));
+}
+
+// Fractional rates 1 < nbits < 2 (AS:352-368, AS:401-411): coordinate k takes the 2-bit table
+// where bit k of its client's mask row is set and the 1-bit table elsewhere.  The tables the
+// kernels get are the 2-bit ones (EdenTables tab; its middle boundary is the 1-bit table's 0.0),
+// and the 1-bit centroids come beside the mask rows.
+struct EdenMask {
+    const uint32_t* bits;    // [rows][ceil(D / 32)] mask rows (KE0m)
+    const int32_t* row;      // [n] row of each client, or null: row 0
+    float lo0, lo1;          // the 1-bit centroids
+};
+__device__ __forceinline__ const uint32_t* mask_row_of(const EdenMask& m, int64_t client, int64_t D) {
+    return m.bits + (int64_t)(m.row ? m.row[client] : 0) * ((D + 31) / 32);
+}
+__device__ __forceinline__ uint32_t mask_bit(const uint32_t* __restrict__ mrow, int64_t i) {
+    return (mrow[i >> 5] >> (i & 31)) & 1u;
+}
+// take(centroids(2), b) where bit is set, else take(centroids(1), b).  Both tables are symmetric
+// (-c reversed, c: AS:309), so the centroid is a magnitude -- the 2-bit table's inner one in bins 1
+// and 2, its outer one in bins 0 and 3, or the 1-bit one -- and a sign, positive from bin 2 (2
+// bits) or in bin 1 (1 bit): bit-field selects of register values, about ten integer operations
+// where eden_cent's masks over four entries take fifteen (the fractional instances are bound by
+// their VALU count).  Only the bin's low two bits are read (its low bit where the mask
+// is clear): the sender writes no other bin, and a foreign message's larger bin decodes as the bin
+// of those bits where the reference's take raises.  lo0 = -lo1 is not read.
+__device__ __forceinline__ float eden_cent_mixed(const EdenCents& t, float lo0, float lo1, int b, uint32_t bit) {
+    (void)lo0;
+    const uint32_t ub = (uint32_t)b, hs = 0u - (bit & 1u);
+    const uint32_t inner = 0u - ((ub ^ (ub >> 1)) & 1u);
+    const uint32_t magh = (inner & __float_as_uint(t.c2)) | (~inner & __float_as_uint(t.c3));
+    const uint32_t mag = (hs & magh) | (~hs & __float_as_uint(lo1));
+    const uint32_t pos = (hs & (ub >> 1)) | (~hs & ub);                 // bit 0: the centroid is positive
+    return __uint_as_float(mag ^ ((pos << 31) ^ 0x80000000u));
 }
 
 // ---- KE0: MT19937 -> diagonal ---------------------------------------------------------
@@ -127,6 +161,66 @@ rht_sign_bits_kernel(const int8_t* __restrict__ signs, int64_t rows, int64_t D, 
     bits[q] = b;
 }
 
+// KE0m: the mask rows of the fractional rates (AS:360-361, AS:402-406): torch.bernoulli(p_high)
+// of a generator seeded with 7 * seed + 13 (its low 32 bits, as init_genrand takes them) draws
+// one word per coordinate, f32(low24) * 2^-24 < f32(p_high), i.e. low24 < thr = ceil(f32(p_high)
+// * 2^24).  One workgroup per row, KE0's twist; bit i % 32 of word i / 32 of the row is
+// coordinate i's draw (rht_sign_bits_kernel's layout).  Two rounds of 624 words are 39 whole
+// mask words, so the draws are packed from LDS after every second round and after the last.
+__global__ void __launch_bounds__(640)
+eden_mask_bits_kernel(const int64_t* __restrict__ seeds, int64_t D, uint32_t thr, uint32_t* __restrict__ bits) {
+    __shared__ uint32_t mt[624];
+    __shared__ uint8_t hit[2 * 624];
+    const int tid = threadIdx.x;
+    const int64_t W = (D + 31) / 32;
+    uint32_t* row = bits + (int64_t)blockIdx.x * W;
+    if (tid == 0) {
+        mt[0] = (uint32_t)((uint64_t)seeds[blockIdx.x] * 7u + 13u);
+        for (int i = 1; i < 624; ++i) mt[i] = 1812433253u * (mt[i - 1] ^ (mt[i - 1] >> 30)) + (uint32_t)i;
+    }
+    __syncthreads();
+    auto twist_word = [&](int i) -> uint32_t {
+        const uint32_t y = (mt[i] & 0x80000000u) | (mt[(i + 1) % 624] & 0x7FFFFFFFu);
+        return mt[(i + 397) % 624] ^ (y >> 1) ^ ((y & 1u) ? 0x9908B0DFu : 0u);
+    };
+    int odd = 0;
+    for (int64_t base = 0; base < D; base += 624, odd ^= 1) {
+        uint32_t nv = 0;
+        if (tid < 227) nv = twist_word(tid);
+        __syncthreads();
+        if (tid < 227) mt[tid] = nv;
+        __syncthreads();
+        if (tid >= 227 && tid < 454) nv = twist_word(tid);
+        __syncthreads();
+        if (tid >= 227 && tid < 454) mt[tid] = nv;
+        __syncthreads();
+        if (tid >= 454 && tid < 624) nv = twist_word(tid);
+        __syncthreads();
+        if (tid >= 454 && tid < 624) mt[tid] = nv;
+        __syncthreads();
+        if (tid < 624) {
+            uint32_t y = mt[tid];
+            y ^= y >> 11;
+            y ^= (y << 7) & 0x9D2C5680u;
+            y ^= (y << 15) & 0xEFC60000u;
+            y ^= y >> 18;
+            hit[odd * 624 + tid] = (y & 0xFFFFFFu) < thr ? 1 : 0;
+        }
+        if (odd || base + 624 >= D) {                    // uniform
+            __syncthreads();
+            const int64_t pair = base - odd * 624;       // a multiple of 1248 = 39 * 32
+            const int64_t w = pair / 32 + tid;
+            if (tid < 39 && w < W) {
+                uint32_t b = 0;
+                for (int k = 0; k < 32; ++k)
+                    if (pair + 32 * tid + k < D) b |= (uint32_t)hit[32 * tid + k] << k;   // (past D: no draw, bit clear)
+                row[w] = b;
+            }
+            __syncthreads();
+        }
+    }
+}
+
 // +-1.0f from bit 0 (set: -1) as an opaque operand, so that the multiply stays a v_mul_f32 as
 // with the int8 rows (the compiler would otherwise fold x * (b ? -1 : 1) into a sign flip,
 // which differs from the multiply on NaN inputs)
@@ -141,7 +235,8 @@ __device__ __forceinline__ float sign_pm1(uint32_t b) {
 // lo > 0: tiles of 2^k rows x 32 columns (row r, column c -> hi + (r << lo) + c0 + c).
 // MODE 0: plain (in -> out, f32).  MODE 1 (first sender pass): in = x rows of length
 // `dim`, zero-padded, times the diagonal.  MODE 2 (first receiver pass): in = u8 bins,
-// value = centroid.  LAST: divide by sqrt(D) as f32 (AS:114); RECV_LAST additionally
+// value = centroid; MODE 3: the same with the table chosen per coordinate by the client's mask
+// row (fractional rates, AS:401-411).  LAST: divide by sqrt(D) as f32 (AS:114); RECV_LAST additionally
 // multiplies by the diagonal and the per-client scale and writes only [0, dim).
 struct FwhtArgs {
     const void* in;
@@ -155,6 +250,85 @@ struct FwhtArgs {
     EdenTables tab;
 };
 
+// (The kernels with a MODE come as a body and two kernels: `<name>_kernel` for MODE 0-2 and
+// `<name>_frac_kernel`, MODE 3, which takes the mask rows beside the arguments.)
+// EDIT TOGETHER with fwht_pass_kernel below (the same text; see the note there).
+template <int MODE, bool LAST, bool RECV_LAST>
+__device__ __forceinline__ void fwht_pass_body(FwhtArgs a, int lo, int k, const EdenMask& mask) {
+    __shared__ float s[1 << (kFwhtHighBits + 5)];        // 4096 (first pass) or 256 x 32
+    const int64_t vec = blockIdx.y;
+    const int tid = threadIdx.x;
+    const int64_t D = a.D;
+    const int cols = lo == 0 ? 1 : kFwhtCols;
+    const int rows = 1 << k;
+    const int tile_elems = rows * cols;
+    const int64_t lowspan = (int64_t)1 << lo;                 // columns available below lo
+    const int64_t col_groups = lo == 0 ? 1 : lowspan / kFwhtCols;
+    const int64_t t = blockIdx.x;
+    const int64_t hi = (t / col_groups) << (lo + k);
+    const int64_t c0 = (t % col_groups) * kFwhtCols;
+    const int8_t* sg = a.signs + (int64_t)(a.sign_row ? a.sign_row[vec] : 0) * D;
+    auto gidx = [&](int e) -> int64_t {                       // tile element -> vector index
+        const int r = lo == 0 ? e : e / kFwhtCols;
+        const int c = lo == 0 ? 0 : e % kFwhtCols;
+        return hi + ((int64_t)r << lo) + c0 + c;
+    };
+    // load (lanes walk columns fastest: 128-byte rows)
+    for (int e = tid; e < tile_elems; e += kFwhtT) {
+        const int64_t i = gidx(e);
+        float v;
+        if (MODE == 1) {
+            const float* x = (const float*)a.in + vec * a.dim;
+            v = i < a.dim ? x[i] : 0.f;
+            v = v * (float)sg[i];                               // AS:132/137 * diag
+        } else if (MODE == 2) {
+            const uint8_t* bins = (const uint8_t*)a.in + vec * D;
+            v = eden_cent(eden_cents(a.tab), bins[i]);          // AS:383 take(centroids, bins)
+        } else if (MODE == 3) {
+            const uint8_t* bins = (const uint8_t*)a.in + vec * D;
+            v = eden_cent_mixed(eden_cents(a.tab), mask.lo0, mask.lo1, bins[i],
+                                mask_bit(mask_row_of(mask, vec, D), i));   // AS:407-411
+        } else {
+            v = ((const float*)a.in)[vec * D + i];
+        }
+        s[e] = v;
+    }
+    __syncthreads();
+    // butterflies over the row bits: rows (r, r + 2^j), bit j of r clear (AS:107-112)
+    const int pairs = (rows >> 1) * cols;
+    for (int j = 0; j < k; ++j) {
+        for (int q = tid; q < pairs; q += kFwhtT) {
+            const int c = q % cols;
+            const int pr = q / cols;
+            const int r = ((pr >> j) << (j + 1)) | (pr & ((1 << j) - 1));
+            const int ea = r * cols + c, eb = (r + (1 << j)) * cols + c;
+            const float av = s[ea], bv = s[eb];
+            const float na = av + bv;
+            s[ea] = na;
+            s[eb] = na - 2.f * bv;
+        }
+        __syncthreads();
+    }
+    for (int e = tid; e < tile_elems; e += kFwhtT) {
+        const int64_t i = gidx(e);
+        float v = s[e];
+        if (LAST) v = v / a.sqrtD;                              // AS:114 vec /= sqrt(d)
+        if (RECV_LAST) {
+            if (i < a.dim) {
+                v = v * (float)sg[i];                           // AS:152 * diag
+                a.out[vec * a.dim + i] = a.scale ? a.scale[vec] * v : v;   // AS:413 scale * vec, [:dim]
+            }
+        } else {
+            a.out[vec * D + i] = v;
+        }
+    }
+}
+
+// EDIT TOGETHER: fwht_pass_kernel below and fwht_pass_body above are one text twice.  The kernel is kept as it
+// was, since as a wrapper of the body its registers were allocated differently and the 1- and 2-bit
+// instances are to stay byte-identical; the body serves the fractional instance alone.  Every fix to
+// one (a bound, an index, a load or store form) goes into the other: the body differs from the kernel
+// only where it reads `mask` (tools/kernel_table.py shows whether the kernel's code moved).
 template <int MODE, bool LAST, bool RECV_LAST>
 __global__ void __launch_bounds__(kFwhtT)
 fwht_pass_kernel(FwhtArgs a, int lo, int k) {
@@ -222,6 +396,11 @@ fwht_pass_kernel(FwhtArgs a, int lo, int k) {
         }
     }
 }
+template <bool LAST, bool RECV_LAST>
+__global__ void __launch_bounds__(kFwhtT)
+fwht_pass_frac_kernel(FwhtArgs a, int lo, int k, EdenMask mask) {
+    fwht_pass_body<3, LAST, RECV_LAST>(a, lo, k, mask);
+}
 
 // ---- KE1': register-radix passes for the two common shapes -----------------------------
 // Same stages in the same order as fwht_pass_kernel (so the same bits), with 16 (low pass)
@@ -248,8 +427,7 @@ __device__ __forceinline__ int pad17(int e) { return e + (e >> 4); }
 // (b1, b2) holds b0 = 0..15 (bits 0-3), round 2 thread (b0, b2) holds b1 (bits 4-7),
 // round 3 thread (b0, b1) holds b2 (bits 8-11).
 template <int MODE, bool LAST, bool RECV_LAST>
-__global__ void __launch_bounds__(256)
-fwht_low4096_kernel(FwhtArgs a) {
+__device__ __forceinline__ void fwht_low4096_body(FwhtArgs a, const EdenMask& mask) {
     __shared__ float s[4096 + 256];
     const int64_t vec = blockIdx.y;
     const int tid = threadIdx.x;
@@ -289,6 +467,19 @@ fwht_low4096_kernel(FwhtArgs a) {
             const uint8_t* bb = reinterpret_cast<const uint8_t*>(&bv);
 #pragma unroll
             for (int i = 0; i < 16; ++i) v[i] = eden_cent(cs, bb[i]);            // AS:383
+        } else if constexpr (MODE == 3) {
+            // The pass is bound by its VALU count (1024 waves per SIMD at 1024 x 2^20: DESIGN 4.3), and
+            // the lookup is most of it: here the six centroids sit in LDS, entry (bin & 3) | mask bit
+            // << 2 (the 1-bit pair twice: only a bin's low bit counts where the mask is clear), one
+            // ds_read per coordinate; lanes read the same word or different banks.
+            __shared__ float cent8[8];
+            if (tid < 8) cent8[tid] = tid >= 4 ? a.tab.c[tid - 4] : (tid & 1) ? mask.lo1 : mask.lo0;
+            const int4 bv = *reinterpret_cast<const int4*>((const uint8_t*)a.in + vec * D + i0);
+            const uint8_t* bb = reinterpret_cast<const uint8_t*>(&bv);
+            const uint32_t mw = mask_row_of(mask, vec, D)[i0 >> 5] >> (i0 & 31);   // 16 mask bits
+            __syncthreads();
+#pragma unroll
+            for (int i = 0; i < 16; ++i) v[i] = cent8[(bb[i] & 3u) | (((mw >> i) & 1u) << 2)];   // AS:407-411
         } else {
             const float* p = (const float*)a.in + vec * D + i0;
 #pragma unroll
@@ -347,13 +538,129 @@ fwht_low4096_kernel(FwhtArgs a) {
     }
 }
 
+template <int MODE, bool LAST, bool RECV_LAST>
+__global__ void __launch_bounds__(256)
+fwht_low4096_kernel(FwhtArgs a) {
+    fwht_low4096_body<MODE, LAST, RECV_LAST>(a, EdenMask{});
+}
+template <bool LAST, bool RECV_LAST>
+__global__ void __launch_bounds__(256)
+fwht_low4096_frac_kernel(FwhtArgs a, EdenMask mask) {
+    fwht_low4096_body<3, LAST, RECV_LAST>(a, mask);
+}
+
 // First pass over 16384 contiguous elements (bits 0-13), for D = 2^22: 14 + 8 bits instead of
 // 12 + 8 + 2, one pass fewer each way.  1024 threads; index e = b0 + 16 b1 + 256 b2 + 4096 b3
 // (b3: 2 bits).  Rounds as fwht_low4096_kernel (b0, b1, b2 in registers in turn, padded LDS
 // transposes), then bits 12-13: a thread takes four columns p = b0 + 16 b1 + 256 b2 and their
 // four b3 values.  The same stages in the same order, so the same bits as 12 + 8 + 2.
 // MODE 0: plain (QUIC-FL's receiver, in place), 1: sender (pad, * diag), 2: receiver (centroids
-// of the bins); never the last pass.
+// of the bins), 3: the fractional receiver (the table by the mask row); never the last pass.
+// EDIT TOGETHER with fwht_low16k_kernel below (the same text; see the note there).
+template <int MODE>
+__device__ __forceinline__ void fwht_low16k_body(FwhtArgs a, const EdenMask& mask) {
+    __shared__ float s[16384 + 1024];
+    const int64_t vec = blockIdx.y;
+    const int tid = threadIdx.x;
+    const int64_t D = a.D;
+    const EdenCents cs = eden_cents(a.tab);
+    const int64_t base = (int64_t)blockIdx.x * 16384;
+    float v[16];
+    {   // round-1 layout: 16 contiguous elements
+        const int64_t i0 = base + (int64_t)tid * 16;
+        if (MODE == 0) {
+            const float* p = (const float*)a.in + vec * D + i0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const float4 t = *reinterpret_cast<const float4*>(p + 4 * q);
+                v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
+            }
+        } else if (MODE == 1) {
+            const int8_t* sg = a.signs + (int64_t)(a.sign_row ? a.sign_row[vec] : 0) * D;
+            const float* x = (const float*)a.in + vec * a.dim;
+            const bool full = i0 + 16 <= a.dim && (((uintptr_t)(x + i0)) & 15) == 0;
+            if (full) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const float4 t = *reinterpret_cast<const float4*>(x + i0 + 4 * q);
+                    v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < 16; ++i) v[i] = (i0 + i < a.dim) ? x[i0 + i] : 0.f;
+            }
+            if (a.sbits) {                                                     // 16 signs as bits
+                const int64_t W = (D + 31) / 32;
+                const uint32_t bw = a.sbits[(int64_t)(a.sign_row ? a.sign_row[vec] : 0) * W + (i0 >> 5)] >> (i0 & 31);
+#pragma unroll
+                for (int i = 0; i < 16; ++i) v[i] = v[i] * sign_pm1(bw >> i);      // AS:132/137 * diag
+            } else {
+                const int4 sgv = *reinterpret_cast<const int4*>(sg + i0);       // 16 signs
+                const int8_t* sb = reinterpret_cast<const int8_t*>(&sgv);
+#pragma unroll
+                for (int i = 0; i < 16; ++i) v[i] = v[i] * (float)sb[i];            // AS:132/137 * diag
+            }
+        } else if (MODE == 2) {
+            const int4 bv = *reinterpret_cast<const int4*>((const uint8_t*)a.in + vec * D + i0);
+            const uint8_t* bb = reinterpret_cast<const uint8_t*>(&bv);
+#pragma unroll
+            for (int i = 0; i < 16; ++i) v[i] = eden_cent(cs, bb[i]);            // AS:383
+        } else {
+            const int4 bv = *reinterpret_cast<const int4*>((const uint8_t*)a.in + vec * D + i0);
+            const uint8_t* bb = reinterpret_cast<const uint8_t*>(&bv);
+            const uint32_t mw = mask_row_of(mask, vec, D)[i0 >> 5] >> (i0 & 31);   // 16 mask bits
+#pragma unroll
+            for (int i = 0; i < 16; ++i) v[i] = eden_cent_mixed(cs, mask.lo0, mask.lo1, bb[i], mw >> i);   // AS:407-411
+        }
+    }
+    const int b3 = tid >> 8, o3 = 4096 * b3;
+    stages16(v);                                                   // bits 0-3
+    {
+        const int b1 = tid & 15, b2 = (tid >> 4) & 15;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) s[pad17(i + 16 * b1 + 256 * b2 + o3)] = v[i];
+    }
+    __syncthreads();
+    const int b0 = tid & 15;
+    {
+        const int b2 = (tid >> 4) & 15;                            // round 2: (b0, b2, b3)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) v[i] = s[pad17(b0 + 16 * i + 256 * b2 + o3)];
+        stages16(v);                                               // bits 4-7
+#pragma unroll
+        for (int i = 0; i < 16; ++i) s[pad17(b0 + 16 * i + 256 * b2 + o3)] = v[i];
+    }
+    __syncthreads();
+    {
+        const int b1 = (tid >> 4) & 15;                            // round 3: (b0, b1, b3)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) v[i] = s[pad17(b0 + 16 * b1 + 256 * i + o3)];
+        stages16(v);                                               // bits 8-11
+#pragma unroll
+        for (int i = 0; i < 16; ++i) s[pad17(b0 + 16 * b1 + 256 * i + o3)] = v[i];
+    }
+    __syncthreads();
+    float* o = a.out + vec * D + base;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {                                  // round 4: bits 12-13
+        const int p = tid + 1024 * j;
+        float w[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) w[k] = s[pad17(p + 4096 * k)];
+        bfly(w[0], w[1]);                                          // bit 12
+        bfly(w[2], w[3]);
+        bfly(w[0], w[2]);                                          // bit 13
+        bfly(w[1], w[3]);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) __builtin_nontemporal_store(w[k], o + p + 4096 * k);
+    }
+}
+
+// EDIT TOGETHER: fwht_low16k_kernel below and fwht_low16k_body above are one text twice.  The kernel is kept as it
+// was, since as a wrapper of the body its registers were allocated differently and the 1- and 2-bit
+// instances are to stay byte-identical; the body serves the fractional instance alone.  Every fix to
+// one (a bound, an index, a load or store form) goes into the other: the body differs from the kernel
+// only where it reads `mask` (tools/kernel_table.py shows whether the kernel's code moved).
 template <int MODE>
 __global__ void __launch_bounds__(1024)
 fwht_low16k_kernel(FwhtArgs a) {
@@ -446,6 +753,10 @@ fwht_low16k_kernel(FwhtArgs a) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) __builtin_nontemporal_store(w[k], o + p + 4096 * k);
     }
+}
+__global__ void __launch_bounds__(1024)
+fwht_low16k_frac_kernel(FwhtArgs a, EdenMask mask) {
+    fwht_low16k_body<3>(a, mask);
 }
 
 // High pass: 256 rows (index bits lo..lo+7) x 64 columns, 512 threads (a wave reads one
@@ -1104,16 +1415,40 @@ __device__ __forceinline__ float eden_thresh(float b, float nv) {
 
 // One client's bins and chains (lane l: chain l); THR: bins by the thresholds T, else by the
 // per-element division (norms that are not positive and finite).  Returns the lane's chain.
-template <int NB, bool THR>
+// FRAC (NB = 3: the 2-bit tables): coordinate i takes the 2-bit bin and centroid where bit i of the
+// client's mask row `mrow` is set, else the 1-bit ones (boundary T[1], centroids lo0 / lo1) --
+// AS:352-368.  A step's 64 coordinates are two mask words, so a register set of U steps holds its
+// 2 U words one per lane (MA / MB); a step reads its two by lane index into a scalar pair, which
+// is the step's lane predicate as it stands (no shift or test per lane).
+template <int NB, bool THR, bool FRAC = false>
 __device__ __forceinline__ float dotbins_chains(const float* __restrict__ vj, int64_t D, float sqrtD, float nv,
                                                 const EdenTables& tab, const EdenCents& cs, const float (&T)[NB],
-                                                uint8_t* __restrict__ bj, int lane) {
+                                                uint8_t* __restrict__ bj, int lane,
+                                                const uint32_t* __restrict__ mrow = nullptr, float lo0 = 0.f,
+                                                float lo1 = 0.f) {
+    static_assert(!FRAC || NB == 3, "the fractional rates mix the 1-bit table into the 2-bit one");
     const __amdgpu_buffer_rsrc_t rv = make_rsrc(vj, (uint32_t)(D * 4));
     const __amdgpu_buffer_rsrc_t rb = make_rsrc(bj, (uint32_t)D);
     float acc = 0.f;
-    auto step = [&](float x, int64_t i) {                                  // bins[i], acc = fma(c[bin], x, acc)
+    auto step = [&](float x, int64_t i, bool hi = false) {                 // bins[i], acc = fma(c[bin], x, acc)
         const float y = x * sqrtD;                                          // AS:329 vec * sqrt(D)
         int b;
+        if (FRAC) {
+            int bl, bh;                                                     // AS:354-355 bins_low, bins_high
+            if (THR) {
+                bl = !(y <= T[1 % NB]) ? 1 : 0;
+                bh = (!(y <= T[0]) ? 1 : 0) + bl + (!(y <= T[2 % NB]) ? 1 : 0);
+            } else {
+                const float q = y / nv;
+                bl = !(tab.b[1] >= q) ? 1 : 0;
+                bh = (!(tab.b[0] >= q) ? 1 : 0) + bl + (!(tab.b[2] >= q) ? 1 : 0);
+            }
+            const uint32_t hs = hi ? ~0u : 0u;
+            b = (int)((hs & (uint32_t)bh) | (~hs & (uint32_t)bl));          // AS:363
+            __builtin_amdgcn_raw_buffer_store_b8((uint8_t)b, rb, (uint32_t)i, 0, 0);
+            acc = fmaf(eden_cent_mixed(cs, lo0, lo1, b, hs), x, acc);       // AS:364-366
+            return;
+        }
         if (THR) {
             b = !(y <= T[0]) ? 1 : 0;
 #pragma unroll
@@ -1128,22 +1463,32 @@ __device__ __forceinline__ float dotbins_chains(const float* __restrict__ vj, in
     auto pipelined = [&](auto u) {                                         // u steps per register set
         constexpr int U = decltype(u)::value;
         float A[U], B[U];
-        auto load = [&](float (&R)[U], int64_t s0) {
+        uint32_t MA = 0u, MB = 0u;
+        auto load = [&](float (&R)[U], uint32_t& M, int64_t s0) {
 #pragma unroll
             for (int k = 0; k < U; ++k)
                 R[k] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
                     rv, (uint32_t)((s0 + k) * 64 + lane) * 4u, 0, kAuxNT));     // beyond D: 0, unused
+            if (FRAC) M = (lane < 2 * U && s0 < steps) ? mrow[2 * s0 + lane] : 0u;   // (steps % U == 0: a whole set)
         };
-        auto run = [&](const float (&R)[U], int64_t s0) {
+        auto run = [&](const float (&R)[U], uint32_t M, int64_t s0) {
 #pragma unroll
-            for (int k = 0; k < U; ++k) step(R[k], (s0 + k) * 64 + lane);
+            for (int k = 0; k < U; ++k) {
+                if (FRAC) {
+                    const uint32_t w0 = (uint32_t)__builtin_amdgcn_readlane((int)M, 2 * k);
+                    const uint32_t w1 = (uint32_t)__builtin_amdgcn_readlane((int)M, 2 * k + 1);
+                    step(R[k], (s0 + k) * 64 + lane, __builtin_amdgcn_inverse_ballot_w64(((uint64_t)w1 << 32) | w0));
+                } else {
+                    step(R[k], (s0 + k) * 64 + lane);
+                }
+            }
         };
-        load(A, 0);
+        load(A, MA, 0);
         for (int64_t s0 = 0; s0 < steps; s0 += 2 * U) {
-            load(B, s0 + U);
-            run(A, s0);
-            load(A, s0 + 2 * U);
-            run(B, s0 + U);
+            load(B, MB, s0 + U);
+            run(A, MA, s0);
+            load(A, MA, s0 + 2 * U);
+            run(B, MB, s0 + U);
         }
     };
     if (steps >= 2 * kDotU && steps % (2 * kDotU) == 0) {
@@ -1154,24 +1499,29 @@ __device__ __forceinline__ float dotbins_chains(const float* __restrict__ vj, in
         pipelined(std::integral_constant<int, kDotU / 2>{});
         return acc;
     }
+    auto at = [&](int64_t i) {
+        if (FRAC) step(vj[i], i, mask_bit(mrow, i) != 0u);
+        else step(vj[i], i);
+    };
     int64_t i0 = 0;
-    for (; i0 + 64 <= D; i0 += 64) step(vj[i0 + lane], i0 + lane);
+    for (; i0 + 64 <= D; i0 += 64) at(i0 + lane);
     if (D - i0 >= 32) {                                                    // remainder: acc 0 and 1
-        if (lane < 32) step(vj[i0 + lane], i0 + lane);
+        if (lane < 32) at(i0 + lane);
         i0 += 32;
     }
     for (; i0 < D; i0 += 16)                                               // then acc 0, masked
         if (lane < 16) {
-            if (i0 + lane < D) step(vj[i0 + lane], i0 + lane);
+            if (i0 + lane < D) at(i0 + lane);
             else acc = fmaf(0.f, 0.f, acc);
         }
     return acc;
 }
 
-template <int NB>       // boundaries: 1 (1 bit) or 3 (2 bits)
-__global__ void __launch_bounds__(64 * kDotWaves)
-eden_dotbins_kernel(const float* __restrict__ v, int64_t D, float sqrtD, const float* __restrict__ nrm, EdenTables tab,
-                    uint8_t* __restrict__ bins, float* __restrict__ scale, int64_t n, const int32_t* __restrict__ redo) {
+template <int NB, bool FRAC>       // boundaries: 1 (1 bit) or 3 (2 bits, and the fractional rates)
+__device__ __forceinline__ void
+dotbins_body(const float* __restrict__ v, int64_t D, float sqrtD, const float* __restrict__ nrm, const EdenTables& tab,
+             uint8_t* __restrict__ bins, float* __restrict__ scale, int64_t n, const int32_t* __restrict__ redo,
+             const EdenMask& mask) {
     __shared__ float red[kDotWaves][64];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int64_t j = (int64_t)blockIdx.x * kDotWaves + wv;
@@ -1186,8 +1536,15 @@ eden_dotbins_kernel(const float* __restrict__ v, int64_t D, float sqrtD, const f
 #pragma unroll
         for (int q = 0; q < NB; ++q) T[q] = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(t), q));
     }
-    const float acc = thr ? dotbins_chains<NB, true>(v + j * D, D, sqrtD, nv, tab, cs, T, bins + j * D, lane)
-                          : dotbins_chains<NB, false>(v + j * D, D, sqrtD, nv, tab, cs, T, bins + j * D, lane);
+    float acc;
+    if (FRAC) {
+        const uint32_t* mrow = mask_row_of(mask, j, D);
+        acc = thr ? dotbins_chains<NB, true, FRAC>(v + j * D, D, sqrtD, nv, tab, cs, T, bins + j * D, lane, mrow, mask.lo0, mask.lo1)
+                  : dotbins_chains<NB, false, FRAC>(v + j * D, D, sqrtD, nv, tab, cs, T, bins + j * D, lane, mrow, mask.lo0, mask.lo1);
+    } else {
+        acc = thr ? dotbins_chains<NB, true>(v + j * D, D, sqrtD, nv, tab, cs, T, bins + j * D, lane)
+                  : dotbins_chains<NB, false>(v + j * D, D, sqrtD, nv, tab, cs, T, bins + j * D, lane);
+    }
     red[wv][lane] = acc;
     wave_lds_fence();
     if (lane == 0) {
@@ -1202,6 +1559,20 @@ eden_dotbins_kernel(const float* __restrict__ v, int64_t D, float sqrtD, const f
         const float dot = (w[0] + w[1]) + (w[2] + w[3]);
         scale[j] = (nv * nv) / dot;                                        // AS:335 norm ** 2 / dot
     }
+}
+
+template <int NB>
+__global__ void __launch_bounds__(64 * kDotWaves)
+eden_dotbins_kernel(const float* __restrict__ v, int64_t D, float sqrtD, const float* __restrict__ nrm, EdenTables tab,
+                    uint8_t* __restrict__ bins, float* __restrict__ scale, int64_t n, const int32_t* __restrict__ redo) {
+    dotbins_body<NB, false>(v, D, sqrtD, nrm, tab, bins, scale, n, redo, EdenMask{});
+}
+
+// KE4 of the fractional rates (AS:352-368): the 2-bit tables, the table per coordinate by the mask row
+__global__ void __launch_bounds__(64 * kDotWaves)
+eden_dotbins_frac_kernel(const float* __restrict__ v, int64_t D, float sqrtD, const float* __restrict__ nrm, EdenTables tab,
+                         uint8_t* __restrict__ bins, float* __restrict__ scale, int64_t n, EdenMask mask) {
+    dotbins_body<3, true>(v, D, sqrtD, nrm, tab, bins, scale, n, nullptr, mask);
 }
 
 // ---- KE4s: the same bins and dot for small batches, its chains cut into segments ----------
@@ -1249,6 +1620,57 @@ __device__ __forceinline__ DotElem dot_elem(const float* thr4, const float* nrm,
     return e;
 }
 
+// The fractional rates (tab: the 2-bit tables): coordinate i of the client takes the 2-bit bin and
+// centroid where its mask bit is set, else the 1-bit ones (AS:352-368)
+struct DotElemF : DotElem {
+    const uint32_t* mrow;
+    float lo0, lo1;
+    __device__ __forceinline__ int bin_at(float x, int64_t i) const {
+        const float y = x * sqrtD;
+        int bl, bh;
+        if (thr) {
+            bl = !(y <= T1) ? 1 : 0;
+            bh = (!(y <= T0) ? 1 : 0) + bl + (!(y <= T2) ? 1 : 0);
+        } else {
+            const float q = y / nv;
+            bl = !(tab.b[1] >= q) ? 1 : 0;
+            bh = (!(tab.b[0] >= q) ? 1 : 0) + bl + (!(tab.b[2] >= q) ? 1 : 0);
+        }
+        return mask_bit(mrow, i) ? bh : bl;
+    }
+    __device__ __forceinline__ float cent_of(int b, int64_t i) const {
+        return eden_cent_mixed(cs, lo0, lo1, b, mask_bit(mrow, i));
+    }
+};
+// one client's element functions by instance: FRAC reads the mask row at the element's index
+template <bool FRAC>
+struct DotSel {
+    typedef DotElem type;
+    static __device__ __forceinline__ DotElem make(const float* thr4, const float* nrm, int64_t j, float sqrtD,
+                                                   const EdenTables& tab, const EdenMask&, int64_t) {
+        return dot_elem(thr4, nrm, j, sqrtD, tab);
+    }
+};
+template <>
+struct DotSel<true> {
+    typedef DotElemF type;
+    static __device__ __forceinline__ DotElemF make(const float* thr4, const float* nrm, int64_t j, float sqrtD,
+                                                    const EdenTables& tab, const EdenMask& mask, int64_t D) {
+        DotElemF e;
+        static_cast<DotElem&>(e) = dot_elem(thr4, nrm, j, sqrtD, tab);
+        e.mrow = mask_row_of(mask, j, D);
+        e.lo0 = mask.lo0;
+        e.lo1 = mask.lo1;
+        return e;
+    }
+};
+__device__ __forceinline__ int bin_at(const DotElem& e, float x, int64_t) { return e.bin(x); }
+__device__ __forceinline__ int bin_at(const DotElemF& e, float x, int64_t i) { return e.bin_at(x, i); }
+__device__ __forceinline__ float cent_of(const DotElem& e, int b, int64_t) { return eden_cent(e.cs, b); }
+__device__ __forceinline__ float cent_of(const DotElemF& e, int b, int64_t i) { return e.cent_of(b, i); }
+__device__ __forceinline__ float cent_at(const DotElem& e, float x, int64_t) { return e.cent(x); }
+__device__ __forceinline__ float cent_at(const DotElemF& e, float x, int64_t i) { return e.cent_of(e.bin_at(x, i), i); }
+
 // KE4p: thresholds per client (lane q: boundary q), thr4[j] = (T0, T1, T2, valid)
 __global__ void __launch_bounds__(64)
 eden_thresh_kernel(const float* __restrict__ nrm, EdenTables tab, float* __restrict__ thr4) {
@@ -1261,14 +1683,17 @@ eden_thresh_kernel(const float* __restrict__ nrm, EdenTables tab, float* __restr
 }
 
 // KE4a: one tile per workgroup; thread (g, l) sums steps 16 g .. 16 g + 15 of chain l
-__global__ void __launch_bounds__(256)
-eden_dseg_sum_kernel(const float* __restrict__ v, int64_t D, float sqrtD, const float* __restrict__ nrm,
-                     const float* __restrict__ thr4, EdenTables tab, uint8_t* __restrict__ bins,
-                     double* __restrict__ segsum) {
+// (The KE4s kernels that look at elements come in two instances of one body: FRAC, the fractional
+// rates' `_frac_kernel`, reads each element's table from the client's mask row.)
+template <bool FRAC>
+__device__ __forceinline__ void
+dseg_sum_body(const float* __restrict__ v, int64_t D, float sqrtD, const float* __restrict__ nrm,
+              const float* __restrict__ thr4, const EdenTables& tab, uint8_t* __restrict__ bins,
+              double* __restrict__ segsum, const EdenMask& mask) {
     __shared__ double part[4][64];
     const int tid = threadIdx.x, l = tid & 63, g = tid >> 6;
     const int64_t client = blockIdx.y, k = blockIdx.x, K = D / kEdenTile;
-    const DotElem de = dot_elem(thr4, nrm, client, sqrtD, tab);
+    const typename DotSel<FRAC>::type de = DotSel<FRAC>::make(thr4, nrm, client, sqrtD, tab, mask, D);
     const float* t = v + client * D + k * kEdenTile;
     uint8_t* bt = bins + client * D + k * kEdenTile;
     float x[16];
@@ -1277,13 +1702,26 @@ eden_dseg_sum_kernel(const float* __restrict__ v, int64_t D, float sqrtD, const 
     double acc = 0.0;                                    // an approximation: any order will do
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-        const int b = de.bin(x[i]);
+        const int64_t ei = k * kEdenTile + 64 * (16 * g + i) + l;
+        const int b = bin_at(de, x[i], ei);
         bt[64 * (16 * g + i) + l] = (uint8_t)b;
-        acc += (double)eden_cent(de.cs, b) * (double)x[i];
+        acc += (double)cent_of(de, b, ei) * (double)x[i];
     }
     part[g][l] = acc;
     __syncthreads();
     if (tid < 64) segsum[(client * 64 + l) * K + k] = (part[0][l] + part[1][l]) + (part[2][l] + part[3][l]);
+}
+__global__ void __launch_bounds__(256)
+eden_dseg_sum_kernel(const float* __restrict__ v, int64_t D, float sqrtD, const float* __restrict__ nrm,
+                     const float* __restrict__ thr4, EdenTables tab, uint8_t* __restrict__ bins,
+                     double* __restrict__ segsum) {
+    dseg_sum_body<false>(v, D, sqrtD, nrm, thr4, tab, bins, segsum, EdenMask{});
+}
+__global__ void __launch_bounds__(256)
+eden_dseg_sum_frac_kernel(const float* __restrict__ v, int64_t D, float sqrtD, const float* __restrict__ nrm,
+                          const float* __restrict__ thr4, EdenTables tab, uint8_t* __restrict__ bins,
+                          double* __restrict__ segsum, EdenMask mask) {
+    dseg_sum_body<true>(v, D, sqrtD, nrm, thr4, tab, bins, segsum, mask);
 }
 
 // KE4b: exclusive prefix per (chain, client) of its K segment sums (the norm's scan, 64 chains)
@@ -1327,15 +1765,16 @@ eden_segscan_l_kernel(const double* __restrict__ segsum, int64_t K, float* __res
 }
 
 // KE4c: thread (tile k, chain l) runs its segment's 64 steps from the guess (the KE2c tests)
-__global__ void __launch_bounds__(256)
-eden_dseg_chain_kernel(const float* __restrict__ v, int64_t D, float sqrtD, const float* __restrict__ nrm,
-                       const float* __restrict__ thr4, EdenTables tab, const float* __restrict__ g,
-                       float* __restrict__ e, int32_t* __restrict__ kind, int32_t* __restrict__ tabcnt,
-                       int32_t* __restrict__ tabseg, int cap) {
+template <bool FRAC>
+__device__ __forceinline__ void
+dseg_chain_body(const float* __restrict__ v, int64_t D, float sqrtD, const float* __restrict__ nrm,
+                const float* __restrict__ thr4, const EdenTables& tab, const float* __restrict__ g,
+                float* __restrict__ e, int32_t* __restrict__ kind, int32_t* __restrict__ tabcnt,
+                int32_t* __restrict__ tabseg, int cap, const EdenMask& mask) {
     const int tid = threadIdx.x, l = tid & 63;
     const int64_t client = blockIdx.y, K = D / kEdenTile;
     const int64_t k = (int64_t)blockIdx.x * kDSegTiles + (tid >> 6);
-    const DotElem de = dot_elem(thr4, nrm, client, sqrtD, tab);
+    const typename DotSel<FRAC>::type de = DotSel<FRAC>::make(thr4, nrm, client, sqrtD, tab, mask, D);
     const float* t = v + client * D + k * kEdenTile + l;
     const int64_t idx = (client * 64 + l) * K + k;
     const float g0 = g[idx];
@@ -1344,7 +1783,7 @@ eden_dseg_chain_kernel(const float* __restrict__ v, int64_t D, float sqrtD, cons
 #pragma unroll 16
     for (int i = 0; i < kSegSteps; ++i) {
         const float x = t[64 * i];
-        const float c = de.cent(x);
+        const float c = cent_at(de, x, k * kEdenTile + l + 64 * i);
         // a negative product (a tiny v whose quotient underflowed into the lowest bin) breaks
         // the chain's monotonicity: list the segment (its table or its steps are sequential)
         tie = tie || (((fbits(c) ^ fbits(x)) >> 31) && x != 0.0f && c != 0.0f);
@@ -1374,8 +1813,67 @@ eden_dseg_chain_kernel(const float* __restrict__ v, int64_t D, float sqrtD, cons
     e[idx] = b;
     kind[idx] = kk;
 }
+__global__ void __launch_bounds__(256)
+eden_dseg_chain_kernel(const float* __restrict__ v, int64_t D, float sqrtD, const float* __restrict__ nrm,
+                       const float* __restrict__ thr4, EdenTables tab, const float* __restrict__ g,
+                       float* __restrict__ e, int32_t* __restrict__ kind, int32_t* __restrict__ tabcnt,
+                       int32_t* __restrict__ tabseg, int cap) {
+    dseg_chain_body<false>(v, D, sqrtD, nrm, thr4, tab, g, e, kind, tabcnt, tabseg, cap, EdenMask{});
+}
+__global__ void __launch_bounds__(256)
+eden_dseg_chain_frac_kernel(const float* __restrict__ v, int64_t D, float sqrtD, const float* __restrict__ nrm,
+                            const float* __restrict__ thr4, EdenTables tab, const float* __restrict__ g,
+                            float* __restrict__ e, int32_t* __restrict__ kind, int32_t* __restrict__ tabcnt,
+                            int32_t* __restrict__ tabseg, int cap, EdenMask mask) {
+    dseg_chain_body<true>(v, D, sqrtD, nrm, thr4, tab, g, e, kind, tabcnt, tabseg, cap, mask);
+}
 
 // KE4t: the listed segment's chain from each of the kSegTab starts around its guess
+// EDIT TOGETHER with eden_dseg_tab_kernel below (the same text; see the note there).
+template <bool FRAC>
+__device__ __forceinline__ void
+dseg_tab_body(const float* __restrict__ v, int64_t D, float sqrtD, const float* __restrict__ nrm,
+              const float* __restrict__ thr4, const EdenTables& tab, const float* __restrict__ g,
+              const int32_t* __restrict__ tabcnt, const int32_t* __restrict__ tabseg, float* __restrict__ tabv,
+              int cap, const EdenMask& mask) {
+    __shared__ float xs[kSegSteps], cs_[kSegSteps];
+    const int64_t client = blockIdx.y;
+    const int slot = blockIdx.x;
+    if (slot >= std::min(tabcnt[client], cap)) return;                   // uniform
+    const int tid = threadIdx.x;
+    const int32_t code = tabseg[client * cap + slot];
+    const int64_t k = code >> 6;
+    const int l = code & 63;
+    const int64_t K = D / kEdenTile;
+    if (tid < kSegSteps) {
+        const typename DotSel<FRAC>::type de = DotSel<FRAC>::make(thr4, nrm, client, sqrtD, tab, mask, D);
+        const float x = v[client * D + k * kEdenTile + 64 * tid + l];
+        xs[tid] = x;
+        cs_[tid] = cent_at(de, x, k * kEdenTile + 64 * tid + l);
+    }
+    __syncthreads();
+    const int64_t gb = fbits(g[(client * 64 + l) * K + k]);
+    constexpr int kPer = kSegTab / 256;
+    float a[kPer];
+#pragma unroll
+    for (int q = 0; q < kPer; ++q) {
+        const int64_t sb = gb + tid + 256 * q - kSegTab / 2;
+        a[q] = sb < 0 ? __uint_as_float(0x7FC00000u) : __uint_as_float((uint32_t)sb);   // (never looked up)
+    }
+    for (int i = 0; i < kSegSteps; ++i) {
+        const float x = xs[i], c = cs_[i];
+#pragma unroll
+        for (int q = 0; q < kPer; ++q) a[q] = fmaf(c, x, a[q]);
+    }
+    float* out = tabv + ((int64_t)client * cap + slot) * kSegTab;
+#pragma unroll
+    for (int q = 0; q < kPer; ++q) out[tid + 256 * q] = a[q];
+}
+// EDIT TOGETHER: eden_dseg_tab_kernel below and dseg_tab_body above are one text twice.  The kernel is kept as it
+// was, since as a wrapper of the body its registers were allocated differently and the 1- and 2-bit
+// instances are to stay byte-identical; the body serves the fractional instance alone.  Every fix to
+// one (a bound, an index, a load or store form) goes into the other: the body differs from the kernel
+// only where it reads `mask` (tools/kernel_table.py shows whether the kernel's code moved).
 __global__ void __launch_bounds__(256)
 eden_dseg_tab_kernel(const float* __restrict__ v, int64_t D, float sqrtD, const float* __restrict__ nrm,
                      const float* __restrict__ thr4, EdenTables tab, const float* __restrict__ g,
@@ -1414,9 +1912,108 @@ eden_dseg_tab_kernel(const float* __restrict__ v, int64_t D, float sqrtD, const 
 #pragma unroll
     for (int q = 0; q < kPer; ++q) out[tid + 256 * q] = a[q];
 }
+__global__ void __launch_bounds__(256)
+eden_dseg_tab_frac_kernel(const float* __restrict__ v, int64_t D, float sqrtD, const float* __restrict__ nrm,
+                          const float* __restrict__ thr4, EdenTables tab, const float* __restrict__ g,
+                          const int32_t* __restrict__ tabcnt, const int32_t* __restrict__ tabseg,
+                          float* __restrict__ tabv, int cap, EdenMask mask) {
+    dseg_tab_body<true>(v, D, sqrtD, nrm, thr4, tab, g, tabcnt, tabseg, tabv, cap, mask);
+}
 
 // KE4d: wave w of workgroup b walks chain 8 b + w of client blockIdx.y (KE2d's walk); the
 // chain's end goes to acc64[client][chain]
+// EDIT TOGETHER with eden_dseg_walk_kernel below (the same text; see the note there).
+template <bool FRAC>
+__device__ __forceinline__ void
+dseg_walk_body(const float* __restrict__ v, int64_t D, float sqrtD, const float* __restrict__ nrm,
+               const float* __restrict__ thr4, const EdenTables& tab, const float* __restrict__ g,
+               const float* __restrict__ e, const int32_t* __restrict__ kind, const float* __restrict__ tabv,
+               float* __restrict__ acc64, int cap, const EdenMask& mask) {
+    const int tid = threadIdx.x, lane = tid & (kWave - 1);
+    const int l = blockIdx.x * 8 + tid / kWave;
+    const int64_t client = blockIdx.y;
+    const int64_t K = D / kEdenTile;
+    const int64_t base = (client * 64 + l) * K;
+    const typename DotSel<FRAC>::type de = DotSel<FRAC>::make(thr4, nrm, client, sqrtD, tab, mask, D);
+    float cg[kWalkChunks], ce[kWalkChunks], ng[kWalkChunks] = {}, ne[kWalkChunks] = {};
+    int32_t ck[kWalkChunks], nk[kWalkChunks] = {};
+    auto fetch = [&](int64_t tile, float (&fg)[kWalkChunks], float (&fe)[kWalkChunks], int32_t (&fk)[kWalkChunks]) {
+#pragma unroll
+        for (int q = 0; q < kWalkChunks; ++q) {
+            const int64_t s = (tile * kWalkChunks + q) * kWave + lane;
+            fg[q] = s < K ? g[base + s] : 0.0f;
+            fe[q] = s < K ? e[base + s] : 0.0f;
+            fk[q] = s < K ? kind[base + s] : 0;
+        }
+    };
+    float A = 0.0f;                                    // wave-uniform
+    int64_t s0 = 0;
+    auto step = [&](int64_t c, float sg, float se, int32_t sk) {
+        const int o = (int)(s0 - c * kWave);
+        const bool inb = lane >= o && c * kWave + lane < K;
+        const bool fin = fexp(sg) < 255 && fexp(se) < 255;
+        const double tau = (inb && fin) ? (double)se - (double)sg : 0.0;   // >= 0: chains never decrease
+        const double Aj = (double)A + wave_prev(wave_incl_scan(tau, lane));
+        const bool span = A > 0.0f && fexp(A) < 255;
+        const double lim = __longlong_as_double((long long)((uint64_t)(std::max(fexp(A), 1) - 127 + 28 + 1023) << 52));
+        const float af = (float)Aj;
+        const float r = af + (float)tau;
+        const bool valid = inb && fin && (lane == o || (span && Aj + tau < lim)) && (double)af == Aj &&
+                           (af == sg || (sk == 0 && fexp(af) == fexp(sg) && fexp(r) == fexp(sg)));
+        const uint64_t bad = __ballot(inb && !valid);
+        const uint64_t inm = __ballot(inb);
+        const int first = bad ? __builtin_ctzll(bad) : 64 - __builtin_clzll(inm);
+        if (first > o) {
+            const float res = af == sg ? se : r;
+            A = __shfl(res, first - 1, kWave);
+            s0 = c * kWave + first;
+            return;
+        }
+        const int32_t kk = __shfl(sk, o, kWave);
+        const float gg = __shfl(sg, o, kWave);
+        bool done = false;
+        if (kk > 0) {
+            const int64_t dd = (int64_t)fbits(A) - (int64_t)fbits(gg) + kSegTab / 2;
+            if (dd >= 0 && dd < kSegTab) {
+                A = tabv[((int64_t)client * cap + (kk - 1)) * kSegTab + dd];
+                done = true;
+            }
+        }
+        if (!done) {
+            const float x = v[client * D + s0 * kEdenTile + 64 * lane + l];
+            const float c = cent_at(de, x, s0 * kEdenTile + 64 * lane + l);
+            for (int i = 0; i < kSegSteps; ++i) {
+                const float xi = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)fbits(x), i));
+                const float ci = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)fbits(c), i));
+                A = fmaf(ci, xi, A);
+            }
+        }
+        s0 += 1;
+    };
+    fetch(0, cg, ce, ck);
+    const int64_t tiles = (K + kWalkChunks * kWave - 1) / (kWalkChunks * kWave);
+    for (int64_t t = 0; t < tiles; ++t) {
+        if (t + 1 < tiles) fetch(t + 1, ng, ne, nk);
+#pragma unroll
+        for (int q = 0; q < kWalkChunks; ++q) {
+            const int64_t c = t * kWalkChunks + q;
+            const int64_t cend = std::min<int64_t>(K, (c + 1) * kWave);
+            while (s0 < cend) step(c, cg[q], ce[q], ck[q]);
+        }
+#pragma unroll
+        for (int q = 0; q < kWalkChunks; ++q) {
+            cg[q] = ng[q];
+            ce[q] = ne[q];
+            ck[q] = nk[q];
+        }
+    }
+    if (lane == 0) acc64[client * 64 + l] = A;
+}
+// EDIT TOGETHER: eden_dseg_walk_kernel below and dseg_walk_body above are one text twice.  The kernel is kept as it
+// was, since as a wrapper of the body its registers were allocated differently and the 1- and 2-bit
+// instances are to stay byte-identical; the body serves the fractional instance alone.  Every fix to
+// one (a bound, an index, a load or store form) goes into the other: the body differs from the kernel
+// only where it reads `mask` (tools/kernel_table.py shows whether the kernel's code moved).
 __global__ void __launch_bounds__(512)
 eden_dseg_walk_kernel(const float* __restrict__ v, int64_t D, float sqrtD, const float* __restrict__ nrm,
                       const float* __restrict__ thr4, EdenTables tab, const float* __restrict__ g,
@@ -1501,6 +2098,13 @@ eden_dseg_walk_kernel(const float* __restrict__ v, int64_t D, float sqrtD, const
         }
     }
     if (lane == 0) acc64[client * 64 + l] = A;
+}
+__global__ void __launch_bounds__(512)
+eden_dseg_walk_frac_kernel(const float* __restrict__ v, int64_t D, float sqrtD, const float* __restrict__ nrm,
+                           const float* __restrict__ thr4, EdenTables tab, const float* __restrict__ g,
+                           const float* __restrict__ e, const int32_t* __restrict__ kind, const float* __restrict__ tabv,
+                           float* __restrict__ acc64, int cap, EdenMask mask) {
+    dseg_walk_body<true>(v, D, sqrtD, nrm, thr4, tab, g, e, kind, tabv, acc64, cap, mask);
 }
 
 // KE4f: the 64 chains in MKL's order, scale = f32(nrm * nrm) / dot (AS:335)

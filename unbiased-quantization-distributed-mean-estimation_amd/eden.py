@@ -5,6 +5,9 @@ Drop-in:
         == NMSE_Results/Codes/All_Schemes.py:792-811: one torch.randint(0, 100) draw of the
         global CPU generator per call (the rotation seed, AS:797), EdenSender.compress then
         EdenReceiver.decompress, returns a NumPy f32 array of length d (AS:811).
+        bits_per_dimension: 1, 2, or any rate between them (EdenSender.stochastic_quantize,
+        AS:352-368: the 2-bit table for a seeded bernoulli(bits - 1) share of the coordinates,
+        the 1-bit table for the rest; no further draw of the global generator).
 
 Batched:
     eden_quantize(x[n, d], bits, seeds[n])              -> out[n, d]
@@ -12,9 +15,11 @@ Batched:
     eden_decompress(msg)                                -> out[n, d]
 
 Numerics: rotation (MT19937 diagonal, f32 butterflies a+b / (a+b)-2b, / f32(sqrt(D))), the
-norm (torch CPU order) and the bins are bit-identical to the reference; the scale's dot
-product is accumulated in fp64 because the reference's (MKL sdot) order is CPU-dependent,
-so outputs agree to 1e-6 relative.  Only the 1- and 2-bit tables exist in the reference.
+norm (torch CPU order), the bins and the scale (its torch.dot in MKL sdot's order on the fixtures'
+host, oracle/uq_eden.py:torch_dot) are bit-identical to the reference, and with them the outputs.
+Only the 1- and 2-bit tables exist in the reference, so the rates are 1, 2 and what lies between them; a fractional message's nbits is the reference's tuple
+(1, 2, p_high).  Rates below 1 (AS:414-423: the receiver drops coordinates by torch.randperm on the
+global generator) raise ValueError.
 """
 from __future__ import annotations
 
@@ -27,7 +32,7 @@ import torch
 from . import _lib, _runtime
 from ._runtime import as_batch_f32, as_vector_f32, ptr, stream_ptr, workspace_for
 
-__all__ = ["EDEN_quantize_Hadamard", "eden_quantize", "eden_compress", "eden_decompress", "EdenMessage",
+__all__ = ["EDEN_quantize_Hadamard", "eden_quantize", "eden_compress", "eden_decompress", "EdenMessage", "eden_mask_bits",
            "rht_signs", "padded_dim", "randomized_hadamard_transform", "randomized_inverse_hadamard_transform"]
 
 _SEEDS = 100                       # AS:797 torch.randint(0, 100)
@@ -185,9 +190,86 @@ def _seeds(seeds, n, generator=None):
 
 
 def _bits(bits):
-    if bits not in (1, 2):
-        raise ValueError("EDEN supports 1 and 2 bits (the reference's centroid tables, AS:302-306)")
-    return int(bits)
+    """1, 2, or the reference's message tuple (1, 2, p_high) for 1 < bits < 2 (AS:386-390: p_high =
+    nbits - floor(nbits) as a Python double).  Anything else has no table in the reference."""
+    if isinstance(bits, (tuple, list)):              # a fractional message's nbits (AS:390; a list: through JSON)
+        try:
+            ok = len(bits) == 3 and bits[0] == 1 and bits[1] == 2 and 0.0 < float(bits[2]) < 1.0
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError("an EDEN message's nbits tuple must be (1, 2, p_high) with 0 < p_high < 1")
+        return (1, 2, float(bits[2]))
+    if isinstance(bits, (str, bytes)):               # float() would parse "1"; the reference compares numbers
+        raise ValueError("EDEN's bits_per_dimension must be a number")
+    try:
+        b = float(bits)                              # Python numbers, NumPy scalars, 0-d tensors
+    except (TypeError, ValueError):
+        raise ValueError("EDEN's bits_per_dimension must be a number") from None
+    if b == 1.0 or b == 2.0:
+        return int(b)
+    if 1.0 < b < 2.0:
+        return (1, 2, b - 1.0)
+    raise ValueError("EDEN supports 1 <= bits <= 2 (the reference's centroid tables, AS:302-306; rates below 1 "
+                     "drop coordinates by torch.randperm on the receiver and are not built)")
+
+
+def _threshold(p_high: float) -> int:
+    """torch.bernoulli draws f32(low24(w)) * 2^-24 < f32(p_high) (AS:361: torch.ones(D) * p_high is an
+    f32 tensor), i.e. low24(w) < ceil(f32(p_high) * 2^24)."""
+    import math
+    import struct
+    p32 = struct.unpack("f", struct.pack("f", p_high))[0]
+    return int(math.ceil(p32 * (1 << 24)))
+
+
+class _MaskCache(_SignCache):
+    """Device mask rows of the fractional rates (uq_eden_mask_bits), kept like the sign tables and
+    keyed like them plus the threshold: a mask row is a pure function of (seed, D, threshold).
+    `builds` counts the tables built (tests: a warm call builds none)."""
+
+    def __init__(self, budget_bytes: int = 1 << 30):
+        super().__init__(budget_bytes)
+        self.builds = 0
+
+
+_masks = _MaskCache()
+_count_lock = threading.Lock()         # of _masks.builds (its own: the cached path builds under _cache_lock)
+
+
+def eden_mask_bits(seeds, D: int, threshold: int, device=None) -> torch.Tensor:
+    """int32 [len(seeds), ceil(D / 32)]: bit k of row r set where coordinate k of a client with
+    rotation seed seeds[r] takes the 2-bit table (AS:360-361, generator seed 7 * seed + 13)."""
+    dev = device or _runtime.device()
+    s = torch.as_tensor(seeds, dtype=torch.int64).reshape(-1).to(dev)
+    out = torch.empty((s.numel(), (D + 31) // 32), dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().uq_eden_mask_bits(ptr(s), s.numel(), D, threshold, ptr(out), stream_ptr(dev)),
+               "uq_eden_mask_bits")
+    with _count_lock:
+        _masks.builds += 1
+    return out
+
+
+def _mask_table(seeds: torch.Tensor, D: int, T: int, dev):
+    """The mask rows in the layout of _sign_rows' table for the same seeds, so that a client's sign
+    row index is its mask row index too: rows of seeds 0..99 when every seed is in that range, the
+    one row of a single other seed, else a row per distinct seed in sorted order."""
+    seeds_cpu = seeds.to("cpu", torch.int64).reshape(-1)
+    if bool(((seeds_cpu >= 0) & (seeds_cpu < _SEEDS)).all()):
+        key, rows, keep = (dev.index, D, T, "ref"), torch.arange(_SEEDS), True
+    elif seeds_cpu.numel() == 1:
+        key, rows, keep = (dev.index, D, T, "one", int(seeds_cpu[0])), seeds_cpu, True
+    else:
+        rows = torch.unique(seeds_cpu)
+        key, keep = (dev.index, D, T, tuple(rows.tolist())), rows.numel() <= 4
+    if not keep:
+        return eden_mask_bits(rows, D, T, dev)
+    with _cache_lock:
+        tab = _masks.get(key)
+        if tab is None:
+            tab = eden_mask_bits(rows, D, T, dev)
+            _masks.put(key, tab)
+        return tab
 
 
 @dataclass
@@ -195,7 +277,7 @@ class EdenMessage:
     bins: torch.Tensor      # u8 [n, D]
     scale: torch.Tensor     # f32 [n]
     seeds: torch.Tensor     # int64 [n] (rotation seeds)
-    nbits: int
+    nbits: object           # 1, 2, or the reference's (1, 2, p_high) for a fractional rate (AS:390)
     dim: int
 
 
@@ -212,6 +294,15 @@ def _call(name, dev, seeds, n, d, D, nb, head, tail):
     if n and d:
         tab, rows, sb = _sign_rows_bits(seeds, D, dev)
         ws = workspace_for("uq_eden_workspace_bytes", dev, n, d)
+        if isinstance(nb, tuple):
+            # uq_eden_<name>_frac_f32(*head, n, d, signs, sign rows, sign bits, mask rows of (D, threshold),
+            # mask row per client = its sign row, *tail, workspace, stream)
+            mb = _mask_table(seeds, D, _threshold(nb[2]), dev)
+            fn = "uq_eden_" + {"compress_f32": "compress_frac_f32", "decompress_f32": "decompress_frac_f32",
+                               "f32": "frac_f32"}[name]
+            _lib.check(getattr(_lib.load(), fn)(*map(ptr, head), n, d, ptr(tab), ptr(rows), ptr(sb), ptr(mb), ptr(rows),
+                                                *map(ptr, tail), ptr(ws), ws.numel(), stream_ptr(dev)), fn)
+            return
         fn = f"uq_eden_{name}_sb"
         _lib.check(getattr(_lib.load(), fn)(*map(ptr, head), n, d, nb, ptr(tab), ptr(rows), ptr(sb), *map(ptr, tail),
                                             ptr(ws), ws.numel(), stream_ptr(dev)), fn)
@@ -235,7 +326,7 @@ def eden_decompress(msg: EdenMessage) -> torch.Tensor:
     n = bins.shape[0]
     d = msg.dim
     out = torch.empty((n, d), dtype=torch.float32, device=dev)
-    _call("decompress_f32", dev, torch.as_tensor(msg.seeds), n, d, bins.shape[1], msg.nbits, (bins, scale), (out,))
+    _call("decompress_f32", dev, torch.as_tensor(msg.seeds), n, d, bins.shape[1], _bits(msg.nbits), (bins, scale), (out,))
     return out
 
 
@@ -285,6 +376,7 @@ def EDEN_quantize_Hadamard(input_vector, bits_per_dimension=1):
     NumPy f32 array (AS:811)."""
     dev = _runtime.device()
     v = as_vector_f32(input_vector, dev)
+    _bits(bits_per_dimension)                            # (a rate without a table raises before the draw)
     seed = int(torch.randint(0, _SEEDS, (1,)).item())
     out = eden_quantize(v.view(1, -1), bits_per_dimension, seeds=[seed])
     # the NumPy result comes back through pinned memory (torch's caching host allocator):
