@@ -95,6 +95,23 @@ constexpr double kEdge = 0x1p-20;
 // staging writes and store reads alike.
 __device__ __forceinline__ int swz(int r, int c) { return r * 16 + 4 * (c ^ (((r >> 2) ^ (r >> 1)) & 3)); }
 __device__ __forceinline__ int swz_elem(int i) { return swz(i >> 4, (i >> 2) & 3) + (i & 3); }
+// The staging writes and the store reads walk the image by float4 index q = tid + j * kQBlock:
+// row (q >> 2) = (tid >> 2) + 64 j, column tid & 3.  64 j leaves the low two bits of r >> 2 and
+// of r >> 1 alone, hence f(r) too, so swz(q >> 2, q & 3) = swz_q0(tid) + j * kQBlock * 4: one
+// address per thread, the rest are immediate offsets.
+__device__ __forceinline__ int swz_q0(int tid) { return swz(tid >> 2, tid & 3); }
+static_assert((kQBlock / 4) % 4 == 0, "swz_q0: a step of kQBlock float4s must keep f(row)");
+
+// A copy of a per-thread index that the compiler cannot see through.  Inside the stream
+// kernels' tile loop every LDS address, byte offset and lane mask derived from tid is loop
+// invariant; hoisted, they outnumber the registers and come back from scratch once per tile
+// (a scratch reload shares vmcnt with the tile's buffer stores and loads, so waiting for one
+// waits for an HBM round trip).  Derived from an opaque copy taken inside the loop body they
+// are recomputed where they are used instead: a few VALU ops per tile.
+__device__ __forceinline__ int opaque(int v) {
+    asm volatile("" : "+v"(v));
+    return v;
+}
 
 struct TileRegs {
     float4 v[kQItems / 4];   // VEC4: float4 q = tid + j*256; scalar: element tid + 256*(4j+c)
@@ -140,11 +157,9 @@ __device__ __forceinline__ void load_tile(TileRegs& r, const float* __restrict__
 template <bool VEC4>
 __device__ __forceinline__ void stage_tile(const TileRegs& r, float* s_x, int tid) {
     if (VEC4) {
+        float* s0 = s_x + swz_q0(tid);              // float4 index tid + j*kQBlock = row*4 + column
 #pragma unroll
-        for (int j = 0; j < kQItems / 4; ++j) {
-            const int q = tid + j * kQBlock;        // float4 index = row*4 + column
-            *reinterpret_cast<float4*>(&s_x[swz(q >> 2, q & 3)]) = r.v[j];
-        }
+        for (int j = 0; j < kQItems / 4; ++j) *reinterpret_cast<float4*>(s0 + j * (kQBlock * 4)) = r.v[j];
     } else {
 #pragma unroll
         for (int j = 0; j < kQItems / 4; ++j) {
@@ -166,10 +181,11 @@ __device__ __forceinline__ void load_tile_buf(TileRegs& r, __amdgpu_buffer_rsrc_
 
 __device__ __forceinline__ void store_tile_buf(const float* s_data, __amdgpu_buffer_rsrc_t ro, uint32_t t0_bytes,
                                                int tid) {
+    const float* s0 = s_data + swz_q0(tid);
 #pragma unroll
     for (int j = 0; j < kQTile / 4 / kQBlock; ++j) {
         const int q = tid + j * kQBlock;
-        const float4 v = *reinterpret_cast<const float4*>(&s_data[swz(q >> 2, q & 3)]);
+        const float4 v = *reinterpret_cast<const float4*>(s0 + j * (kQBlock * 4));
         const f32x4v w = {v.x, v.y, v.z, v.w};
         __builtin_amdgcn_raw_buffer_store_b128(w, ro, t0_bytes + (uint32_t)q * 16u, 0, kAuxNT);
     }
@@ -296,6 +312,7 @@ __device__ __forceinline__ double* slot_of(float* s_scr, int t) { return reinter
 
 // Cumulative tie correction of the last tie thread before `tid` (slot[3]), 0 if none.
 __device__ __forceinline__ double tie_corr(float* s_scr, const ScanLds& sl, int tid) {
+    tid = opaque(tid);
     const int lane = tid & (kWave - 1);
     int w = tid / kWave;
     uint64_t mk = sl.tmask[w] & ((1ull << lane) - 1ull);
@@ -380,6 +397,7 @@ struct IrrThread {
 };
 __device__ void irregular_prep(double Ps, const TileState& st, const TileVals& tv, float* s_scr, ScanLds& sl, int tid,
                                IrrThread& it) {
+    tid = opaque(tid);
     double* slot = slot_of(s_scr, tid);
     const int wid = tid / kWave;
     const int lane = tid & (kWave - 1);
@@ -449,6 +467,7 @@ __device__ void irregular_prep(double Ps, const TileState& st, const TileVals& t
 // scratch, so the caller may rewrite the image right after.
 __device__ double resolve_exact(double P, const Binade& B, const TileState& st, const TileVals& tv, float* s_scr,
                                 ScanLds& sl, int tid, double& pnext) {
+    tid = opaque(tid);
     double* slot = slot_of(s_scr, tid);
     if (P >= 32.0 && (P + st.total) + 1.0 < B.top) {            // regular (uniform)
         int nt = 0;
@@ -664,6 +683,7 @@ __device__ __forceinline__ void tile_pass2(float* s_o, const TileVals& tv, const
 
 template <bool CVEC>
 __device__ __forceinline__ void store_codes(int8_t* __restrict__ ct, const uint32_t (&cw)[4], int len, int tid) {
+    if (!CVEC) tid = opaque(tid);               // the bytewise form's 16 addresses: not worth registers
     const int i0 = tid * kQItems;
     if (CVEC && i0 + kQItems <= len) {
         const u32x4v v = {cw[0], cw[1], cw[2], cw[3]};
@@ -734,11 +754,23 @@ __device__ __forceinline__ void store_tile(const float* s_data, float* __restric
 // the GPU (batched DME, the bench workload).  Requires d % 4 == 0 and 4*d < 2^31
 // (buffer addressing); the host uses the per-tile form otherwise.
 //
-// Order of the vector-memory operations per iteration t: stores of tile t-1 (q from the
-// LDS image s_o, codes from registers), THEN the loads of tile t+1.  vmcnt counts stores
-// too and retires in issue order, so with the loads last the wait before staging tile
-// t+1 never waits on a store acknowledgement, and stores and loads both overlap the
-// whole compute of tile t.
+// Order of the vector-memory operations per iteration t: stores of tile t-1 (q from the LDS
+// image s_o, codes from registers), THEN the loads of tile t+1.  vmcnt counts stores too and
+// retires in issue order, so with the loads last the waits before staging tile t+1 (vmcnt 3,
+// 2, 1, 0: the loop's only waits on vector memory) wait for nothing younger than the loads,
+// and stores and loads both overlap the whole compute of tile t.  The loop keeps no scratch
+// (tools/k2_codegen.py, tests/test_k2_codegen.py): the per-thread addresses are one swizzled
+// base plus immediates (swz_q0), and the rare paths derive theirs from an opaque copy of tid
+// instead of holding them across the loop.
+//
+// The 4-bit form (kCodesEarly) stores the codes of tile t as soon as pass 2 has them, at the
+// end of iteration t.  That store is then the youngest operation at the staging waits, so the
+// last of them also waits for its acknowledgement, and the q stores and the loads go out
+// after it.  Measured, not designed: an earlier build reloaded spilled addresses from scratch
+// between the tile's first store and the others and so waited for that store by accident;
+// with no store acknowledged before the others go out the step's K2 takes 1.69 ms instead of
+// 1.63 ms (every output placement shifts alike); waiting for all the stores, for the second
+// q store, or sleeping instead does not help.
 //
 // Segments: workgroup b takes client b / nseg, tiles [s*seg_tiles, (s+1)*seg_tiles) with
 // s = b % nseg, starting from the exact P = pre[first tile] (the per-client fold of the
@@ -762,13 +794,14 @@ __device__ __forceinline__ void stream_tiles(const float* __restrict__ x, float*
     build_table(s_tab, tid, L, fm);
     uint32_t cw[4] = {0u, 0u, 0u, 0u};
     float kmax = 0.0f;
+    constexpr bool kCodesEarly = WQ && WC && NIB;   // see above; only the 4-bit form was measured
     for (int32_t tile = tb; tile < te; ++tile) {
         stage_tile<true>(pre_x, s_x, tid);
         __syncthreads();                           // s_x(t) staged; s_o(t-1) complete
         if (tile > tb) {
             const uint32_t tp = (uint32_t)(tile - 1) * (uint32_t)kQTile;
             if (WQ) store_tile_buf(s_o, ro, tp * 4u, tid);      // beyond d: dropped by the range check
-            if (WC) store_codes_buf<CVEC, NIB>(rc, codes + vec * ldc, cw, tp, d, tid);
+            if (WC && !kCodesEarly) store_codes_buf<CVEC, NIB>(rc, codes + vec * ldc, cw, tp, d, tid);
         }
         if (tile + 1 < te) load_tile_buf(pre_x, rx, (uint32_t)(tile + 1) * (uint32_t)(kQTile * 4), tid);
         const int64_t t0 = (int64_t)tile * kQTile;
@@ -785,13 +818,14 @@ __device__ __forceinline__ void stream_tiles(const float* __restrict__ x, float*
         double pnext;
         const double base = resolve_exact(P, B, st, tv, s_x, sl, tid, pnext);
         tile_pass2<WQ, WC, NIB>(s_o, tv, s_tab, tid, base, L, fm, Xv, cw, kmax);
+        if (kCodesEarly) store_codes_buf<CVEC, NIB>(rc, codes + vec * ldc, cw, (uint32_t)tile * (uint32_t)kQTile, d, tid);
         P = pnext;
     }
     __syncthreads();
     const uint32_t tp = (uint32_t)(te - 1) * (uint32_t)kQTile;
     if (WQ) store_tile_buf(s_o, ro, tp * 4u, tid);
     if (WC) {
-        store_codes_buf<CVEC, NIB>(rc, codes + vec * ldc, cw, tp, d, tid);
+        if (!kCodesEarly) store_codes_buf<CVEC, NIB>(rc, codes + vec * ldc, cw, tp, d, tid);
         if (nseg == 1)
             store_kmax_block(kmax, L, overflow, vec, tid, reinterpret_cast<int*>(sl.wave));
         else
