@@ -1,5 +1,5 @@
-"""What the K2 kernels compile to: registers, spills, scratch, LDS, and the vector-memory waits
-inside the stream kernels' tile loop.  CPU only (cross-compiles for gfx950).
+"""What the K2 kernels compile to: registers, spills, scratch, LDS, the vector-memory waits inside
+the stream kernels' tile loop and its vector-ALU instruction counts.  CPU only (cross-compiles for gfx950).
 
     python tools/k2_codegen.py [--csrc DIR] [--git REV] [--keep-asm FILE]
 
@@ -10,7 +10,9 @@ quantize_small_kernel instantiation it prints the code object's metadata (.vgpr_
 and for the tile loop of each (the largest depth-1 loop of the kernel, nested loops included)
 every s_waitcnt that names vmcnt: its line in the kernel's assembly, its value and the
 instruction that follows it.  Spills are read from the metadata only; the one mnemonic the tool
-looks for is s_waitcnt.
+looks for is s_waitcnt.  It also counts the vector-ALU instructions (v_*) of each tile loop: all of
+them, and those of the hot blocks a full regular tile runs per element (tile_loop_valu), which for
+quantize_stream_kernel<1,1,1,1>, the bench step's instantiation, are listed block by block.
 
 report() returns the same as a dict (tests/test_k2_codegen.py).
 """
@@ -26,6 +28,7 @@ PKG = os.path.join(ROOT, "unbiased-quantization-distributed-mean-estimation_amd"
 KEYS = (".vgpr_count", ".vgpr_spill_count", ".sgpr_spill_count", ".private_segment_fixed_size",
         ".group_segment_fixed_size")
 KERNELS = ("quantize_stream_kernel", "quantize_small_kernel")
+HOT_DETAIL = "quantize_stream_kernel<1,1,1,1>"      # the bench step's instantiation: hot path block by block
 
 
 def _build_ext():
@@ -107,9 +110,9 @@ _HDR = re.compile(r"^\.LBB(\d+_\d+):.*=>This Loop Header: Depth=1")
 _IN = re.compile(r"(?:in Loop: Header=|Parent Loop )BB(\d+_\d+) Depth=1")
 
 
-def tile_loop_waits(body):
-    """Blocks of the kernel by depth-1 loop (from the assembler's loop comments); the largest such
-    loop is the tile loop.  Returns (header label, [(line, vmcnt, next instruction)])."""
+def _loop_owner(body):
+    """For every line of the kernel the depth-1 loop it belongs to (from the assembler's loop
+    comments, nested loops included), or None."""
     owner, cur, pend = [], None, False
     for l in body:
         s = l.strip()
@@ -126,13 +129,24 @@ def tile_loop_waits(body):
         elif s and not s.startswith(";"):
             pend = False
         owner.append(cur)
+    return owner
+
+
+def _tile_loop(owner):
     sizes = {}
     for o in owner:
         if o:
             sizes[o] = sizes.get(o, 0) + 1
-    if not sizes:
+    return max(sizes, key=sizes.get) if sizes else None
+
+
+def tile_loop_waits(body):
+    """Blocks of the kernel by depth-1 loop; the largest such loop is the tile loop.  Returns
+    (header label, [(line, vmcnt, next instruction)])."""
+    owner = _loop_owner(body)
+    loop = _tile_loop(owner)
+    if loop is None:
         return None, []
-    loop = max(sizes, key=sizes.get)
     waits = []
     for i, l in enumerate(body):
         s = l.strip()
@@ -140,6 +154,63 @@ def tile_loop_waits(body):
             nxt = next((b.strip() for b in body[i + 1:] if b.strip() and not b.strip().startswith(";")), "")
             waits.append((i + 1, int(re.search(r"vmcnt\((\d+)\)", s).group(1)), nxt.split(";")[0].strip()))
     return loop, waits
+
+
+def tile_loop_valu(body):
+    """Vector-ALU instructions (mnemonic v_*) of the tile loop, counted statically.
+
+    in_loop: every v_* instruction in the loop's blocks, rare paths and nested loops included.
+    hot: the v_* instructions of the straight-line blocks that every thread runs once per full,
+    regular tile (kQItems = 16 elements), found by what only they hold:
+      div4    the blocks with packed fmas (the Markstein quotients, four elements each).  Each of
+              the loop's two tile_pass1 instantiations (FULL and padded) has its own identical
+              copies; kQItems / 4 of them run per tile, and the cheapest that many are counted;
+      pass 1  the block with kQItems v_floor_f32 and kQItems v_cvt_f64_f32 and no v_cvt_f32_f64,
+              and the blocks after it through the first with an s_barrier (the wave scan, what
+              the compiler sinks below it, the tile sums); of the two instantiations the cheaper
+              one is the full tile's;
+      pass 2  the blocks with v_cvt_f32_f64 and v_floor_f32 (the f32 crossing of the fp64 prefix),
+              and the block the last of them falls into (the packing and the early codes store).
+    The tie resolution and the staging are not in it.  Returns (in_loop, hot, [(block, part,
+    v_* count)])."""
+    owner = _loop_owner(body)
+    loop = _tile_loop(owner)
+    if loop is None:
+        return 0, 0, []
+    blocks, cur = [], None
+    for i, l in enumerate(body):
+        s = l.strip()
+        if l.startswith(".LBB") or s.startswith("; %bb."):
+            cur = None
+            if owner[i] == loop:
+                cur = {"name": l[1:l.index(":")].replace("; %", "") if l.startswith(".LBB") else s[3:s.index(":")],
+                       "v": 0, "floor": 0, "to32": 0, "to64": 0, "pk": 0, "barrier": 0}
+                blocks.append(cur)
+            continue
+        if cur is None or not s or s.startswith(";") or s.startswith("."):
+            continue
+        mn = s.split()[0]
+        cur["v"] += mn.startswith("v_")
+        cur["floor"] += mn.startswith("v_floor_f32")
+        cur["to32"] += mn.startswith("v_cvt_f32_f64")
+        cur["to64"] += mn.startswith("v_cvt_f64_f32")
+        cur["pk"] += mn.startswith("v_pk_fma_f32")
+        cur["barrier"] += mn == "s_barrier"
+    in_loop = sum(b["v"] for b in blocks)
+    path = [(b["name"], "div4", b["v"]) for b in sorted((b for b in blocks if b["pk"]), key=lambda b: b["v"])[:4]]
+    inst = []
+    for j, b in enumerate(blocks):
+        if b["floor"] >= 16 and b["to64"] >= 16 and not b["to32"] and not b["pk"]:
+            k = next((k for k in range(j, len(blocks)) if blocks[k]["barrier"]), j)
+            inst.append(blocks[j:k + 1])
+    if inst:
+        run = min(inst, key=lambda r: sum(b["v"] for b in r))
+        path += [(b["name"], "pass 1", b["v"]) for b in run if b["v"]]
+    p2 = [j for j, b in enumerate(blocks) if b["to32"] and b["floor"]]
+    path += [(blocks[j]["name"], "pass 2", blocks[j]["v"]) for j in p2]
+    if p2 and p2[-1] + 1 < len(blocks):
+        path.append((blocks[p2[-1] + 1]["name"], "pass 2 tail", blocks[p2[-1] + 1]["v"]))
+    return in_loop, sum(n for _, _, n in path), path
 
 
 def report(csrc=None, rev=None, keep_asm=None):
@@ -160,8 +231,12 @@ def report(csrc=None, rev=None, keep_asm=None):
         name = instantiation(sym)
         if name is None:
             continue
-        loop, waits = tile_loop_waits(kernel_body(asm, sym)) if name.startswith(KERNELS[0]) else (None, [])
-        out[name] = {"meta": md, "loop": loop, "waits": waits}
+        stream = name.startswith(KERNELS[0])
+        body = kernel_body(asm, sym) if stream else []
+        loop, waits = tile_loop_waits(body) if stream else (None, [])
+        in_loop, hot, path = tile_loop_valu(body) if stream else (0, 0, [])
+        out[name] = {"meta": md, "loop": loop, "waits": waits, "valu_loop": in_loop, "valu_hot": hot,
+                     "hot_path": path}
     return out
 
 
@@ -172,6 +247,7 @@ def main():
     ap.add_argument("--keep-asm")
     a = ap.parse_args()
     rep = report(a.csrc, a.git, a.keep_asm)
+    print("# csrc of %s" % (a.git or a.csrc or "the tree"))
     for name in sorted(rep):
         r = rep[name]
         print(name)
@@ -182,6 +258,12 @@ def main():
         print(f"    tile loop {r['loop']}: {len(r['waits'])} s_waitcnt naming vmcnt")
         for line, val, nxt in r["waits"]:
             print(f"        line {line:<6} vmcnt({val})  then  {nxt}")
+        print(f"    v_* instructions in the tile loop: {r['valu_loop']}")
+        print(f"    v_* instructions in the hot blocks (div4, pass 1, pass 2 of a full tile): {r['valu_hot']} per "
+              f"thread and tile, {r['valu_hot'] / 16:.2f} per element")
+        if name == HOT_DETAIL:
+            for blk, part, n in r["hot_path"]:
+                print(f"        {blk:<12}{part:<12}{n}")
     return 0
 
 

@@ -142,30 +142,34 @@ __device__ __forceinline__ DivPlan div_plan_norm(float nv) {
     return p;
 }
 typedef float f32x2 __attribute__((ext_vector_type(2)));
+// PZ: no quotient is -0 (a recomputed one has + 0.0f added, which changes nothing else).  The
+// Markstein steps themselves never give -0: a quotient that is not recomputed has
+// |q2| >= thr > 0, or x = +-0, and then q2 = +0 (x = -0: q0 = -0, r = fma(-den, -0, -0) = +0,
+// q1 = fma(+0, y, -0) = +0, r = fma(-den, +0, -0) = -0, q2 = fma(-0, y, +0) = +0; x = +0: +0
+// at every step).  tools/pass1_sign_check.c checks this over every f32 x.
+template <bool PZ = false>
 __device__ __forceinline__ void div4(const float (&xs)[4], const DivPlan& dp, float (&vs)[4]) {
     if (dp.fast) {
         const f32x2 Y = {dp.y, dp.y}, B = {-dp.den, -dp.den};
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const f32x2 a = {xs[2 * h], xs[2 * h + 1]};
-            f32x2 q = a * Y;
-            f32x2 r = __builtin_elementwise_fma(B, q, a);
-            q = __builtin_elementwise_fma(r, Y, q);
-            r = __builtin_elementwise_fma(B, q, a);
-            q = __builtin_elementwise_fma(r, Y, q);
-            vs[2 * h] = q.x;
-            vs[2 * h + 1] = q.y;
-        }
+        // the two pairs step by step side by side: each step's two packed operations are
+        // independent, so neither waits a cycle for the result of the one before it
+        const f32x2 a0 = {xs[0], xs[1]}, a1 = {xs[2], xs[3]};
+        f32x2 q0 = a0 * Y, q1 = a1 * Y;
+        f32x2 r0 = __builtin_elementwise_fma(B, q0, a0), r1 = __builtin_elementwise_fma(B, q1, a1);
+        q0 = __builtin_elementwise_fma(r0, Y, q0), q1 = __builtin_elementwise_fma(r1, Y, q1);
+        r0 = __builtin_elementwise_fma(B, q0, a0), r1 = __builtin_elementwise_fma(B, q1, a1);
+        q0 = __builtin_elementwise_fma(r0, Y, q0), q1 = __builtin_elementwise_fma(r1, Y, q1);
+        vs[0] = q0.x, vs[1] = q0.y, vs[2] = q1.x, vs[3] = q1.y;
         // one test per four: the smallest |q| (q is finite here: den >= |x| and finite)
         const float mn = fminf(fminf(fabsf(vs[0]), fabsf(vs[1])), fminf(fabsf(vs[2]), fabsf(vs[3])));
         if (__builtin_expect(!(mn >= dp.thr), 0)) {
 #pragma unroll
             for (int c = 0; c < 4; ++c)
-                if (!(fabsf(vs[c]) >= dp.thr) && xs[c] != 0.0f) vs[c] = xs[c] / dp.den;
+                if (!(fabsf(vs[c]) >= dp.thr) && xs[c] != 0.0f) vs[c] = PZ ? xs[c] / dp.den + 0.0f : xs[c] / dp.den;
         }
     } else {
 #pragma unroll
-        for (int c = 0; c < 4; ++c) vs[c] = xs[c] / dp.den;
+        for (int c = 0; c < 4; ++c) vs[c] = PZ ? xs[c] / dp.den + 0.0f : xs[c] / dp.den;
     }
 }
 // One quotient, the same operations as div4 (so the same bits).

@@ -261,15 +261,32 @@ __device__ __forceinline__ void tile_pass1(const float* s_x, TileVals& tv, ScanL
         const float4 xv4 = *reinterpret_cast<const float4*>(&s_x[swz(tid, k4)]);
         const float xs[4] = {xv4.x, xv4.y, xv4.z, xv4.w};
         float vs[4];
-        div4(xs, dp, vs);                       // AS:625 x / den, correctly rounded
+        if (__builtin_expect(dp.fast, 1)) {
+            div4<true>(xs, dp, vs);             // AS:625 x / den, correctly rounded; never -0
+        } else {
+            // the IEEE division (div4's other branch).  Only here can a quotient be NaN (L1 is
+            // not finite); it goes on with its sign cleared, as |v| did
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const float q = xs[c] / dp.den + 0.0f;
+                vs[c] = q != q ? fabsf(q) : q;
+            }
+        }
+        const f32x2 F = {fm, fm};
+        const f32x2 pr[2] = {F * f32x2{vs[0], vs[1]}, F * f32x2{vs[2], vs[3]}};    // the quotients' own pairs
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            const float v = vs[c];
-            const float p = fabsf(v);           // AS:626
-            const float mp = fm * p;            // AS:629
+            // mp = fm*|v| (AS:626, AS:629) with sign(v) folded in, as one product: rounding to
+            // nearest is symmetric, so RN(fm*v) = -RN(fm*|v|) for v < 0.  v = -0 is not "v < 0"
+            // (its mps was +0): the quotients come without it (div4<true>; + 0.0f turns -0 into
+            // +0 and changes no other value, a NaN stays that NaN).  |.| below is a source
+            // modifier.  tools/pass1_sign_check.c compares this with
+            // v < 0 ? -(fm*|v|) : fm*|v| over every f32 v.
+            const float mps0 = (c & 1) ? pr[c >> 1].y : pr[c >> 1].x;
+            const float mp = fabsf(mps0);
             const float fl = floorf(mp);        // AS:630
             float fr = mp - fl;                 // AS:631
-            float mps = v < 0.0f ? -mp : mp;
+            float mps = mps0;
             if (!FULL && i0 + 4 * k4 + c >= len) fr = mps = 0.0f;
             tv.mps[4 * k4 + c] = mps;
             c0 += (double)fr;                   // AS:635, from a parity-0 start
@@ -628,7 +645,7 @@ __device__ bool resolve_map(double Pg, const Binade& B, const TileState& st, flo
 
 // Wire code of one coordinate (type codes, see uq_dme.h): k = fl + r ->
 // code = k for sign(v) >= 0 and ~k = -k-1 for sign(v) < 0 (keeps the reference's -0.0
-// outputs).  kmax (float) tracks the largest k; a client whose kmax > 127 is flagged as
+// outputs).  kmax tracks the largest k; a client whose kmax > 127 is flagged as
 // overflow (its codes are meaningless).  fl is finite whenever L1 is finite, and a
 // non-finite L1 flags the client separately (publish_kmax).
 __device__ __forceinline__ uint32_t code_of(float mps, float kf) {
@@ -638,19 +655,46 @@ __device__ __forceinline__ uint32_t code_of(float mps, float kf) {
 
 // pass 2; WQ: outputs into the LDS image s_o, WC: this thread's 16 codes into cw (NIB: as
 // 4-bit codes, element e of the thread in bits 4e..4e+3 of cw[0..1]).
+//
+// The count k = fl + r is kept as an integer: k = (int)fl + (c_i crossed), with the float
+// kf = fl + r re-derived only where it can matter.  While kf < 2^24 both are the same number
+// ((int) of an integral float and + 1 are exact), so the table index, the code and the
+// running max are the same bits; a group of four with any k >= kTab, or a client whose L1 is
+// not finite, recomputes its elements from the float kf exactly as before.  That covers every
+// case in which the two could differ: fl >= 2^24 (the float sum rounds), fl >= 2^31 (the
+// conversion saturates; as unsigned the count stays >= kTab even after + 1) and fl = NaN (only
+// when L1 is not finite).  kmax is only ever compared with 127.
+//
+// The rare path is one rolled loop per group (the element picked by selects on the uniform
+// loop counter): unrolled it was most of the loop's code.
+__device__ __forceinline__ uint32_t sign_mask(float mps) { return (uint32_t)((int)__float_as_uint(mps) >> 31); }
+// The difference as a value of its own: left to itself the compiler pairs two of a group's
+// subtractions into one packed add and spends three moves on lining its operands up.
+__device__ __forceinline__ float own_f32(float v) {
+    asm("" : "+v"(v));
+    return v;
+}
+template <typename T>
+__device__ __forceinline__ T pick4(const T (&a)[4], int c) {
+    return c == 0 ? a[0] : c == 1 ? a[1] : c == 2 ? a[2] : a[3];
+}
+
 template <bool WQ, bool WC, bool NIB = false>
 __device__ __forceinline__ void tile_pass2(float* s_o, const TileVals& tv, const float* s_tab, int tid, double base,
-                                           float L, float fm, float Xv, uint32_t (&cw)[4], float& kmax) {
+                                           float L, float fm, float Xv, uint32_t (&cw)[4], uint32_t& kmax) {
     double s = base;                           // exact prefix before this thread's first element
     float fprev = floorf((float)s - Xv);       // floor(c_{i-1} - X) of this thread's first element
     // k = fl + r can only be NaN when L1 is not finite: such a client takes the arithmetic
     // path for every element; otherwise a running max of k bounds the table reads
     const bool arith = !(fabsf(L) <= 3.40282347e38f);
+    constexpr uint32_t kLim = (uint32_t)kTab;
+    constexpr int kBits = NIB ? 4 : 8;
+    constexpr uint32_t kMask = (1u << kBits) - 1u;
 #pragma unroll
     for (int k4 = 0; k4 < kQItems / 4; ++k4) {
-        float o[4], kfs[4];
-        float m4 = 0.0f;
-        uint32_t w = 0;
+        float o[4];
+        uint32_t ks[4];
+        uint32_t m4 = 0, w = 0;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             const float mps = tv.mps[4 * k4 + c];
@@ -658,22 +702,35 @@ __device__ __forceinline__ void tile_pass2(float* s_o, const TileVals& tv, const
             const float fla = floorf(mp);                      // AS:630
             s += (double)(mp - fla);                           // AS:631, AS:635 fp64 running sum
             const float fcur = floorf((float)s - Xv);          // AS:636 floor(c_i - X)
-            const float r = (fcur - fprev == 1.0f) ? 1.0f : 0.0f;   // AS:636-637
+            const uint32_t k = (uint32_t)(int)fla + (own_f32(fcur - fprev) == 1.0f ? 1u : 0u);   // AS:636-637, fl + r
             fprev = fcur;
-            const float kf = fla + r;                          // fl + r
-            kfs[c] = kf;
-            m4 = fmaxf(m4, kf);
+            ks[c] = k;
+            m4 = max(m4, k);
             // AS:640 via the table, sign(v) from mps; k >= kTab is recomputed below (rare)
-            if (WQ) o[c] = copysignf(s_tab[(int)kf & (kTab - 1)], mps);
-            if (WC) w |= NIB ? (code_of(mps, kf) & 0xFu) << (4 * c)       // padding elements: mps = 0, r = 0
-                             : code_of(mps, kf) << (8 * c);
+            // (k ^ sign mask) & kMask as one three-input bit operation (truth table 0x48 over
+            // a, b, c: (a ^ c) & b); padding elements: mps = 0, r = 0
+            const uint32_t code = __builtin_amdgcn_bitop3_b32(sign_mask(mps), kMask, k, 0x48);
+            if (WQ) o[c] = copysignf(s_tab[k & (kTab - 1)], mps);
+            if (WC) w |= code << (kBits * c);
         }
-        if (WC) kmax = fmaxf(kmax, m4);
-        if (WQ && __builtin_expect(!(m4 < (float)kTab) || arith, 0)) {
+        if (WC) kmax = max(kmax, m4);
+        if (__builtin_expect(!(m4 < kLim) || (WQ && arith), 0)) {
+            const float ms[4] = {tv.mps[4 * k4], tv.mps[4 * k4 + 1], tv.mps[4 * k4 + 2], tv.mps[4 * k4 + 3]};
+#pragma unroll 1
+            for (int c = 0; c < 4; ++c) {
+                const float mps = pick4(ms, c);
+                const uint32_t k = pick4(ks, c);
+                if (!(k < kLim) || (WQ && arith)) {
+                    const float fla = floorf(fabsf(mps));
+                    const float kf = fla + (float)(k - (uint32_t)(int)fla);        // fl + r, r = 0 or 1
+                    if (WQ) {
+                        const float oc = (copysignf(L, mps) * kf) / fm;             // ((L1*sign)*(fl+r))/m
 #pragma unroll
-            for (int c = 0; c < 4; ++c)
-                if (!(kfs[c] < (float)kTab) || arith)
-                    o[c] = (copysignf(L, tv.mps[4 * k4 + c]) * kfs[c]) / fm;   // ((L1*sign)*(fl+r))/m
+                        for (int e = 0; e < 4; ++e) o[e] = c == e ? oc : o[e];
+                    }
+                    if (WC) w = (w & ~(kMask << (kBits * c))) | ((code_of(mps, kf) & kMask) << (kBits * c));
+                }
+            }
         }
         if (WQ) *reinterpret_cast<float4*>(&s_o[swz(tid, k4)]) = make_float4(o[0], o[1], o[2], o[3]);
         if (WC && !NIB) cw[k4] = w;
@@ -711,8 +768,8 @@ __device__ __forceinline__ void store_codes_buf(__amdgpu_buffer_rsrc_t rc, int8_
     }
 }
 
-__device__ __forceinline__ void publish_kmax(float kmaxf, float L, int32_t* kmaxv, int64_t vec, int tid) {
-    int kmax = (kmaxf <= 127.0f && isfinite(L)) ? (int)kmaxf : 128;     // 128 = overflow / not codable
+__device__ __forceinline__ void publish_kmax(uint32_t kmaxu, float L, int32_t* kmaxv, int64_t vec, int tid) {
+    int kmax = (kmaxu <= 127u && isfinite(L)) ? (int)kmaxu : 128;     // 128 = overflow / not codable
 #pragma unroll
     for (int o = kWave / 2; o > 0; o >>= 1) kmax = max(kmax, __shfl_xor(kmax, o, kWave));
     if ((tid & (kWave - 1)) == 0) atomicMax(&kmaxv[vec], kmax);
@@ -720,9 +777,9 @@ __device__ __forceinline__ void publish_kmax(float kmaxf, float L, int32_t* kmax
 // The whole client in this workgroup (the stream form with nseg == 1): the block's max is
 // the client's, stored plainly -- kmax needs no zero-fill before the launch (one memset per
 // call less: ~5 us of the bench step).  s_red: kQBlock / kWave ints of LDS.
-__device__ __forceinline__ void store_kmax_block(float kmaxf, float L, int32_t* kmaxv, int64_t vec, int tid,
+__device__ __forceinline__ void store_kmax_block(uint32_t kmaxu, float L, int32_t* kmaxv, int64_t vec, int tid,
                                                  int* s_red) {
-    int kmax = (kmaxf <= 127.0f && isfinite(L)) ? (int)kmaxf : 128;
+    int kmax = (kmaxu <= 127u && isfinite(L)) ? (int)kmaxu : 128;
 #pragma unroll
     for (int o = kWave / 2; o > 0; o >>= 1) kmax = max(kmax, __shfl_xor(kmax, o, kWave));
     if ((tid & (kWave - 1)) == 0) s_red[tid / kWave] = kmax;
@@ -793,7 +850,7 @@ __device__ __forceinline__ void stream_tiles(const float* __restrict__ x, float*
     load_tile_buf(pre_x, rx, (uint32_t)tb * (uint32_t)(kQTile * 4), tid);
     build_table(s_tab, tid, L, fm);
     uint32_t cw[4] = {0u, 0u, 0u, 0u};
-    float kmax = 0.0f;
+    uint32_t kmax = 0u;
     constexpr bool kCodesEarly = WQ && WC && NIB;   // see above; only the 4-bit form was measured
     for (int32_t tile = tb; tile < te; ++tile) {
         stage_tile<true>(pre_x, s_x, tid);
@@ -1332,7 +1389,7 @@ tile_out_kernel(const float* __restrict__ x, float* __restrict__ out, int8_t* __
     double pnext;
     const double base = resolve_exact(P, B, st, tv, s_x, sl, tid, pnext);   // barrier-terminated if it used s_x
     uint32_t cw[4];
-    float kmax = 0.0f;
+    uint32_t kmax = 0u;
     tile_pass2<WQ, WC>(s_x, tv, s_tab, tid, base, L, fm, Xs ? Xs[vec] : Xval, cw, kmax);   // each thread rewrites its own row
     if (WC) {
         store_codes<CVEC>(codes + vec * ldc + t0, cw, len, tid);
