@@ -115,6 +115,7 @@ int uq_test_last_unbiased_plan(int64_t* plan_out, int32_t cap);
  *   the mode the call takes when a row is ambiguous)   [2] replay form (UQ_BIASED_REPLAY_*)
  *   KB7a's levels (0 without them): [3] levels, [4] of which before KB6 starts, [5] workgroups
  *   per level launch   [6] S: replay slots, min(n, 256)   [7] vec4: 16-byte accesses to x and out
+ *   (in a codes call also 4-byte ones to the codes rows)
  *   [8] cand_multi: the candidate digits over [9] cspans workgroups per client   [10] cap: u32 of
  *   the candidate region per client   [11] capf = cap / 2: listed pairs per client at most
  *   [12] output tiles per client   [13] clear_bits: the tie bits are cleared by a memset
@@ -124,7 +125,8 @@ int uq_test_last_unbiased_plan(int64_t* plan_out, int32_t cap);
  * uq_test_biased_plan: host only, launches nothing: the plan of a call of that shape and policy
  * (alignment as flags), with uq_type_biased_f32's own checks of n, d and tie_policy.  Front 0
  * for n == 0 or d == 0.
- * uq_test_last_biased_plan: the plan of this thread's last uq_type_biased_f32 call (front 0
+ * uq_test_last_biased_plan: the plan of this thread's last uq_type_biased_f32 or
+ * uq_type_biased_codes_f32 call (front 0
  * when it launched nothing). */
 #define UQ_BIASED_PLAN_FIELDS 15
 #define UQ_BIASED_FRONT_NONE 0
@@ -326,6 +328,24 @@ int uq_codes_q_mean_ld_f32(const int8_t* codes, int64_t ldc, const float* q, int
                            const int32_t* kmax, int64_t n, int64_t d, int64_t m, float n_div,
                            int32_t accumulate, float* est, void* stream);
 
+/* The two forms of type codes (not the UQ_FORM_* plan forms above).  Both are lattice types
+ * k/m with the same int8 code (k for sign > 0 or >= 0, -k-1 for sign < 0), but the dequantized
+ * value groups its products differently, so each form has its own decode and mean tables:
+ *   UQ_FORM_UNBIASED  |q| = RN(RN(L1*k) / f32(m))     (AS:640; uq_type_unbiased_codes_f32)
+ *   UQ_FORM_BIASED    |q| = RN(L1 * RN(k / f32(m)))   (AS:687; uq_type_biased_codes_f32), m >= 1
+ * uq_codes_decode_form_f32 / uq_codes_mean_form_f32: as uq_codes_decode_f32 /
+ * uq_codes_q_mean_ld_f32 (q may be NULL) for codes of `form`; UQ_FORM_UNBIASED gives the bits
+ * of those entries, any other value of form is UQ_E_INVALID.  With UQ_FORM_BIASED the mean is
+ * bit-identical to uq_client_mean_f32 over uq_type_biased_f32's output for clients with
+ * kmax[j] <= 127; a client with kmax[j] == 128 is read from q (required for such a batch). */
+#define UQ_FORM_UNBIASED 0
+#define UQ_FORM_BIASED 1
+int uq_codes_decode_form_f32(const int8_t* codes, const float* l1, int64_t n, int64_t d, int64_t m, int32_t form,
+                             float* out, void* stream);
+int uq_codes_mean_form_f32(const int8_t* codes, int64_t ldc, const float* q, int64_t ldq, const float* l1,
+                           const int32_t* kmax, int64_t n, int64_t d, int64_t m, int32_t form, float n_div,
+                           int32_t accumulate, float* est, void* stream);
+
 /* ---- type messages "UQR1": entropy-coded type codes ---------------
  * The reference has no wire format (parity unpinned); its client output is AS:640's
  * dequantized vector, fully described by (L1, m, signed counts k) = the int8 codes above.
@@ -335,6 +355,10 @@ int uq_codes_q_mean_ld_f32(const int8_t* codes, int64_t ldc, const float* q, int
  * flags bit 0 (UQ_TC_EXACT_ZERO_SIGNS): keep the sign of zero counts (neg for k = 0), so
  * the decoded q is bit-identical to AS:640 (-0.0 included); without it the sign of a zero
  * count is dropped and q is value-identical (+0.0 where the reference has -0.0), at ~R bits.
+ * flags bit 1 (UQ_TC_BIASED_FORM): the codes are of UQ_FORM_BIASED; the bit is written into the
+ * header's flags half-word (byte 6) beside bit 0 and changes nothing else of the message: the
+ * coder does not depend on it and uq_tc_decode accepts either value (the receiver reads the
+ * form from the header).  Messages without it are byte for byte what they have always been.
  * Byte layout: oracle/uq_codec.c (the CPU restatement the tests compare against).
  *
  * uq_tc_bound: the largest message of a client of length d (bytes).
@@ -347,6 +371,7 @@ int uq_codes_q_mean_ld_f32(const int8_t* codes, int64_t ldc, const float* q, int
  *   outside the buffer), bit 1 bad frequency table, bit 2 word stream overrun or underrun,
  *   bit 3 wrong final state, bit 4 the header's m differs from `m` (m < 0: any m). */
 #define UQ_TC_EXACT_ZERO_SIGNS 1
+#define UQ_TC_BIASED_FORM 2
 int uq_tc_bound(int64_t d, size_t* bytes_out);
 int uq_tc_workspace_bytes(int64_t n, int64_t d, size_t* bytes_out);
 int uq_tc_encode(const int8_t* codes, const float* l1, int64_t n, int64_t d, int64_t m, int32_t flags,
@@ -386,6 +411,33 @@ int uq_biased_workspace_bytes(int64_t n, int64_t d, int32_t torch_threads, size_
 int uq_type_biased_f32(const float* x, float* out, int64_t n, int64_t d, int64_t m,
                        int32_t torch_threads, int32_t tie_policy, float* l1_out, int32_t* info,
                        void* ws, size_t ws_bytes, void* stream);
+
+/* uq_type_biased_f32 that also (out given) or only (out == NULL: no float output is written at
+ * all) writes the type codes of the same k'': codes [n][d] int8 of UQ_FORM_BIASED, kmax [n] int32
+ * (written by the call) and l1_out [n] (required: the codes are decoded with it).  Same tie
+ * policies, host-check bit and info pairs as uq_type_biased_f32, and the same bits in out.
+ * Workspace: uq_biased_codes_workspace_bytes (uq_biased_workspace_bytes plus one int32 per
+ * 4096 coordinates and client, where the writers gather the largest coded count); the same
+ * buffer serves both calls.  m >= 1.
+ *   code = k''      for x > 0
+ *   code = -k''-1   for x < 0  (a negative coordinate with k'' = 0 is -0.0 and round-trips)
+ *   code = 0        for x == 0 (sign 0: the output is +0.0 whatever k'' the Delta < 0 adjustment
+ *                   gave the coordinate; so the counts of the codes sum to <= m, to m when no
+ *                   coordinate is zero)
+ * For a client with kmax[j] <= 127, uq_codes_decode_form_f32(UQ_FORM_BIASED) of (codes, l1_out, m)
+ * is out bit for bit.  kmax[j] is >= every coded count of the row and <= the largest + 1 (a
+ * count written provisionally and lowered by a patch may leave it one high); it is 128 for a
+ * client whose codes must not be decoded: a count above 127 at any stage (saturated to 127 in
+ * the code), L1 not finite, or info flag bit 1 (m' not finite) or bit 2 (|Delta| > d).  Such
+ * rows are still correct in out when out is given.
+ * Errors (UQ_E_INVALID with a uq_last_error text): m < 1; codes, kmax or l1_out NULL with
+ * n, d > 0.  n == 0 or d == 0 is a no-op.  16-byte accesses need x and out 16-byte aligned, the
+ * codes 4-byte aligned and d % 4 == 0 (the plan's vec4; any alignment gives the same bits).
+ * uq_test_last_biased_plan reports this call's plan too. */
+int uq_biased_codes_workspace_bytes(int64_t n, int64_t d, int32_t torch_threads, size_t* bytes_out);
+int uq_type_biased_codes_f32(const float* x, float* out, int8_t* codes, int32_t* kmax, int64_t n, int64_t d,
+                             int64_t m, int32_t torch_threads, int32_t tie_policy, float* l1_out, int32_t* info,
+                             void* ws, size_t ws_bytes, void* stream);
 
 /* ---- EDEN with the randomized Hadamard transform (baseline) -------
  * NMSE_Results/Codes/All_Schemes.py:95-153 (RHT), :324-413 (EdenSender / EdenReceiver),

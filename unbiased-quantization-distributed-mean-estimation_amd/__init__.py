@@ -13,7 +13,7 @@ from .quantizer import (
     quantize_encode, decode, codes_mean,
 )
 from .codes import TypeCodes, TypeMessages, encode_messages, decode_messages
-from .biased import Type_biased_quantize, biased_quantize
+from .biased import Type_biased_quantize, biased_quantize, biased_quantize_encode, biased_quantize_mean
 from .eden import (EDEN_quantize_Hadamard, eden_quantize, eden_compress, eden_decompress, EdenMessage, rht_signs,
                    randomized_hadamard_transform, randomized_inverse_hadamard_transform)
 from .quicfl import (QuicFLReceiver, QuicFLSender, QuicFLMessages, QUICFL_quantize, quicfl_compress,
@@ -37,7 +37,8 @@ __all__ = [
     "quantize_mean", "l1_torch_order", "draw_uniforms", "set_torch_threads", "get_torch_threads",
     "check_status", "UQError", "load_library", "library_path", "shard_range", "sharded_client_mean",
     "sharded_quantize_mean", "DISTRIBUTIONS", "Suspended", "legacy_draw", "nmse_simulation", "quantize_encode", "decode", "codes_mean",
-    "TypeCodes", "Type_biased_quantize", "biased_quantize", "EDEN_quantize_Hadamard", "eden_quantize",
+    "TypeCodes", "Type_biased_quantize", "biased_quantize", "biased_quantize_encode", "biased_quantize_mean",
+    "EDEN_quantize_Hadamard", "eden_quantize",
     "eden_compress", "eden_decompress", "EdenMessage", "rht_signs", "randomized_hadamard_transform",
     "randomized_inverse_hadamard_transform", "compute_nmse_stats_auto", "data_format", "round_nmse",
     "DMEPipeline", "codes4_fits", "ShardedDME", "TypeMessages", "encode_messages", "decode_messages", "set_output_pool",

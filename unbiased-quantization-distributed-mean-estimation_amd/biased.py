@@ -8,6 +8,11 @@ Drop-in:
 
 Batched:
     biased_quantize(x[n, d], bits | m=, ties="torch" | "lowest") -> out[n, d]
+    biased_quantize_encode(x[n, d], bits | m=, ...)              -> TypeCodes(form="biased") [, q]
+    biased_quantize_mean(x[n, d], bits, n_div, ...)              -> est[d]  (codes only, then the mean from codes)
+
+Type codes: the lattice type k''/m of AS:661/665 as int8 codes with L1 and m (codes.py): one byte
+per coordinate instead of four; quantizer.decode rebuilds biased_quantize's output bit for bit.
 
 Numerics (all f32, as torch CPU): k' = floor(m*p + 0.5), m' = k'.sum() in torch CPU order
 for `torch_threads`, Delta = int(m' - m), the |Delta| extreme delta' = k' - m*p adjusted by
@@ -23,9 +28,10 @@ import torch
 
 from . import _lib, _runtime
 from ._runtime import as_batch_f32, as_vector_f32, check_status, get_torch_threads, ptr, stream_ptr, workspace_for
+from .codes import TypeCodes
 from .rates import RATE_TABLE, rate_to_m
 
-__all__ = ["Type_biased_quantize", "biased_quantize", "TIES_TORCH", "TIES_LOWEST_INDEX",
+__all__ = ["Type_biased_quantize", "biased_quantize", "biased_quantize_encode", "biased_quantize_mean", "TIES_TORCH", "TIES_LOWEST_INDEX",
            "FLAG_AMBIGUOUS", "FLAG_NONFINITE", "FLAG_RANGE", "FLAG_TORCH_TIES"]
 
 TIES_TORCH = 0            # UQ_TIES_TORCH
@@ -76,6 +82,52 @@ def biased_quantize(x, bits_per_dimension=1, *, m: int | None = None, torch_thre
     if return_info:
         res.append(info)
     return res[0] if len(res) == 1 else tuple(res)
+
+
+def biased_quantize_encode(x, bits_per_dimension=1, *, m: int | None = None, torch_threads: int | None = None,
+                           ties="torch", host_check: bool = False, with_q: bool = False):
+    """Batched Type_biased_quantize as type codes: TypeCodes(form="biased"), or (TypeCodes, q)
+    with with_q (q == biased_quantize's output bit for bit).  Without with_q no float output is
+    written at all.  quantizer.decode(tc) == q bit for bit for every row with tc.overflow <= 127;
+    a row with tc.overflow == 128 (a count above 127, or a non-finite L1 or m') must be sent as
+    floats: TypeCodes.check() raises for it, as for the unbiased codes.  m >= 1."""
+    dev = _runtime.device()
+    x = as_batch_f32(x, dev)
+    n, d = x.shape
+    mm = int(m) if m is not None else rate_to_m(bits_per_dimension, d)
+    T = get_torch_threads() if torch_threads is None else int(torch_threads)
+    if ties not in _TIES:
+        raise ValueError("ties must be 'torch' or 'lowest'")
+    codes = torch.empty((n, d), dtype=torch.int8, device=dev)
+    q = torch.empty_like(x) if with_q else None
+    kmax = torch.zeros(n, dtype=torch.int32, device=dev)
+    l1 = torch.zeros(n, dtype=torch.float32, device=dev)
+    ws = workspace_for("uq_biased_codes_workspace_bytes", dev, n, d, T)
+    policy = _TIES[ties] | (_HOST_CHECK if host_check and _TIES[ties] == TIES_TORCH else 0)
+    _lib.check(_lib.load().uq_type_biased_codes_f32(ptr(x), ptr(q), ptr(codes), ptr(kmax), n, d, mm, T, policy, ptr(l1),
+                                                    ptr(None), ptr(ws), ws.numel(), stream_ptr(dev)),
+               "uq_type_biased_codes_f32")
+    tc = TypeCodes(codes=codes, l1=l1, m=mm, overflow=kmax, form="biased")
+    return (tc, q) if with_q else tc
+
+
+def biased_quantize_mean(x, bits_per_dimension=1, n_div=None, *, m: int | None = None,
+                         torch_threads: int | None = None, ties="torch", host_check: bool = False, est=None,
+                         accumulate: bool = False):
+    """Quantize every row with the biased type quantizer and fold the client-ordered mean
+    (ND:133-138): est (+)= biased_quantize(x)[j] / n_div, bit-identical to
+    client_mean(biased_quantize(x), n_div).  Runs codes only (no float batch is written) and
+    folds the mean from the codes.  This costs one synchronisation: the rows' kmax is read
+    back, and when a row is flagged (kmax 128: its codes must not be decoded) the batch is
+    quantized again through the float path and the flagged rows are read from it."""
+    from .quantizer import codes_mean
+    tc = biased_quantize_encode(x, bits_per_dimension, m=m, torch_threads=torch_threads, ties=ties, host_check=host_check)
+    if n_div is None:
+        n_div = tc.n
+    q = None
+    if tc.n and bool((tc.overflow > 127).any().item()):
+        q = biased_quantize(x, m=tc.m, torch_threads=torch_threads, ties=ties, host_check=host_check)
+    return codes_mean(tc, n_div, est=est, accumulate=accumulate, q=q)
 
 
 def _flags_and_status(dev, d: int, info) -> int:

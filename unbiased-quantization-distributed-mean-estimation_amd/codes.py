@@ -22,9 +22,22 @@ include/uq_dme.h uq_tc_*): ~R bits per coordinate (0.99 at R = 1, 1.92 at R = 2 
 d = 2^20 Gaussian clients).  Parity unpinned: the reference has no codec; decode(encode) is
 checked against AS:640's output (values, and bits with exact_zero_signs).
 
+The biased type quantizer (`Type_biased_quantize`, AS:644-687; biased.biased_quantize_encode)
+produces the same kind of object, a lattice type k''/m, in the same int8 code, but dequantizes
+with its products grouped differently:
+
+    q_i    = (L1 * sign(v_i)) * RN(k''_i / f32(m))            (== AS:687 bit-for-bit)
+
+so a TypeCodes carries its `form` ("unbiased" | "biased") and decode / codes_mean / the UQR1
+header follow it.  In the biased form a coordinate with v_i == 0 has code 0 whatever k'' the
+Delta < 0 adjustment gave it (sign 0: the output is +0.0), so the counts sum to <= m; m >= 1; and
+`overflow` is 128 also for a client with a non-finite L1 or m' (its codes must not be decoded).
+
 Serialized message (little endian):
-    b"UQT1" | u32 version=1 | i64 n | i64 d | i64 m | f32 l1[n] | i8 codes[n*d]
-(the per-client max count is recomputed from the codes on receipt)
+    b"UQT1" | u32 version=1 | i64 n | i64 d | i64 m | f32 l1[n] | i8 codes[n*d]          unbiased
+    b"UQT1" | u32 version=2 | i64 n | i64 d | i64 m | u32 form | f32 l1[n] | i8 codes[n*d]
+(version 2 is written for biased codes only, form 1 = biased; the per-client max count is
+recomputed from the codes on receipt)
 """
 from __future__ import annotations
 
@@ -40,7 +53,17 @@ from ._runtime import ptr, stream_ptr
 
 MAGIC = b"UQT1"
 VERSION = 1
+VERSION_FORM = 2              # the header is followed by a u32 form
 _HDR = struct.Struct("<4sIqqq")
+FORMS = ("unbiased", "biased")             # index = UQ_FORM_* of include/uq_dme.h
+TC_BIASED_FORM = 2                         # UQ_TC_BIASED_FORM: flags bit 1 of a UQR1 header
+
+
+def form_index(form: str) -> int:
+    """UQ_FORM_* of a TypeCodes / TypeMessages form; ValueError for an unknown one."""
+    if form not in FORMS:
+        raise ValueError(f"form must be one of {FORMS}, not {form!r}")
+    return FORMS.index(form)
 
 
 @dataclass
@@ -49,6 +72,7 @@ class TypeCodes:
     l1: torch.Tensor         # f32 [n]
     m: int                   # lattice sum (AS:623)
     overflow: torch.Tensor   # int32 [n]: the client's largest count k; 128 = a count > 127 saturated
+    form: str = "unbiased"   # which dequantize form the codes decode with (FORMS)
 
     @property
     def n(self) -> int:
@@ -66,7 +90,10 @@ class TypeCodes:
 
     def to_bytes(self) -> bytes:
         self.check()
-        hdr = _HDR.pack(MAGIC, VERSION, self.n, self.d, int(self.m))
+        fi = form_index(self.form)
+        hdr = _HDR.pack(MAGIC, VERSION_FORM if fi else VERSION, self.n, self.d, int(self.m))
+        if fi:
+            hdr += struct.pack("<I", fi)
         l1 = self.l1.detach().to("cpu", torch.float32).contiguous().numpy().astype("<f4").tobytes()
         c = self.codes.detach().to("cpu").contiguous().numpy().astype(np.int8).tobytes()
         return hdr + l1 + c
@@ -74,9 +101,15 @@ class TypeCodes:
     @classmethod
     def from_bytes(cls, buf: bytes, device=None) -> "TypeCodes":
         magic, ver, n, d, m = _HDR.unpack_from(buf, 0)
-        if magic != MAGIC or ver != VERSION:
+        if magic != MAGIC or ver not in (VERSION, VERSION_FORM):
             raise ValueError("not a UQT1 type-codes message")
         off = _HDR.size
+        fi = 0
+        if ver == VERSION_FORM:
+            (fi,) = struct.unpack_from("<I", buf, off)
+            off += 4
+            if fi >= len(FORMS):
+                raise ValueError(f"unknown type-codes form {fi}")
         l1 = np.frombuffer(buf, dtype="<f4", count=n, offset=off).astype(np.float32)
         off += 4 * n
         codes = np.frombuffer(buf, dtype=np.int8, count=n * d, offset=off).reshape(n, d)
@@ -86,7 +119,7 @@ class TypeCodes:
         k = np.where(codes < 0, -(codes.astype(np.int32)) - 1, codes.astype(np.int32))
         kmax = k.max(axis=1) if d else np.zeros(n, np.int32)
         return cls(codes=torch.from_numpy(codes.copy()).to(dev), l1=torch.from_numpy(l1).to(dev), m=int(m),
-                   overflow=torch.from_numpy(kmax.astype(np.int32)).to(dev))
+                   overflow=torch.from_numpy(kmax.astype(np.int32)).to(dev), form=FORMS[fi])
 
 
 @dataclass
@@ -99,6 +132,7 @@ class TypeMessages:
     d: int
     m: int
     exact_zero_signs: bool
+    form: str = "unbiased"   # of the codes inside (header flags bit 1)
 
     def sizes(self) -> np.ndarray:
         o = self.offsets.cpu().numpy().astype(np.int64)
@@ -122,14 +156,17 @@ class TypeMessages:
     @classmethod
     def from_messages(cls, msgs, d: int, device=None) -> "TypeMessages":
         """Pack host messages (bytes) of one batch for decode_messages.  Every header must
-        carry the same m and flags (one batch is decoded and averaged with one m; ValueError
-        otherwise); the decoder then checks each message in full, and flags (status bit 4) any
+        carry the same m, flags and form (one batch is decoded and averaged with one m and one
+        table form; ValueError otherwise); the decoder then checks each message in full, and flags (status bit 4) any
         whose m differs from the batch's."""
         for j, b in enumerate(msgs):
             if len(b) < 40 or b[:4] != b"UQR1":
                 raise ValueError(f"message {j} is not a UQR1 message")
         ms = {struct.unpack_from("<Q", b, 16)[0] for b in msgs}
         fl = {struct.unpack_from("<H", b, 6)[0] & 1 for b in msgs}
+        fo = {(struct.unpack_from("<H", b, 6)[0] >> 1) & 1 for b in msgs}
+        if len(fo) > 1:
+            raise ValueError("messages of one batch must share their form (biased and unbiased codes are mixed)")
         if len(ms) > 1 or len(fl) > 1:
             raise ValueError(f"messages of one batch must share m and flags (m: {sorted(ms)[:4]}, flags: {sorted(fl)})")
         # each message starts 4-byte aligned (the decoder reads 32-bit words); sizes are
@@ -143,7 +180,7 @@ class TypeMessages:
         exact = bool(fl.pop()) if msgs else False
         dev = device or "cuda"
         return cls(data=torch.from_numpy(buf.copy()).to(dev), offsets=torch.from_numpy(off).to(dev), n=len(msgs),
-                   d=int(d), m=int(m), exact_zero_signs=exact)
+                   d=int(d), m=int(m), exact_zero_signs=exact, form=FORMS[fo.pop()] if msgs else "unbiased")
 
 
 def _tc_sizes(lib, n, d):
@@ -173,7 +210,7 @@ def encode_messages(tc: "TypeCodes", exact_zero_signs: bool = False,
     l1 = tc.l1.to(device=dev, dtype=torch.float32).contiguous()
     n, d = codes.shape
     tc.check()
-    flags = 1 if exact_zero_signs else 0
+    flags = (1 if exact_zero_signs else 0) | (TC_BIASED_FORM if form_index(tc.form) else 0)
     bound, _ = _tc_sizes(lib, n, d)
     chunk = n if n * bound <= staging_bytes else max(1, staging_bytes // max(1, bound))
 
@@ -187,7 +224,8 @@ def encode_messages(tc: "TypeCodes", exact_zero_signs: bool = False,
         data = torch.empty(max(1, n * bound), dtype=torch.uint8, device=dev)
         offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
         encode(0, n, data, offsets, torch.empty(max(1, wsb), dtype=torch.uint8, device=dev))
-        return TypeMessages(data=data, offsets=offsets, n=n, d=d, m=int(tc.m), exact_zero_signs=bool(exact_zero_signs))
+        return TypeMessages(data=data, offsets=offsets, n=n, d=d, m=int(tc.m), exact_zero_signs=bool(exact_zero_signs),
+                            form=tc.form)
     _, wsb = _tc_sizes(lib, chunk, d)
     stage = torch.empty(chunk * bound, dtype=torch.uint8, device=dev)
     soff = torch.empty(chunk + 1, dtype=torch.int64, device=dev)
@@ -201,7 +239,7 @@ def encode_messages(tc: "TypeCodes", exact_zero_signs: bool = False,
         offs.append(soff[1:nj + 1] + base)
         base += tot
     return TypeMessages(data=torch.cat(parts), offsets=torch.cat(offs), n=n, d=d, m=int(tc.m),
-                        exact_zero_signs=bool(exact_zero_signs))
+                        exact_zero_signs=bool(exact_zero_signs), form=tc.form)
 
 
 def decode_messages(msgs: TypeMessages) -> "TypeCodes":
@@ -220,4 +258,4 @@ def decode_messages(msgs: TypeMessages) -> "TypeCodes":
     bad = int(torch.count_nonzero(status[:n]).item()) if n else 0
     if bad:
         raise ValueError(f"{bad} malformed UQR1 message(s) (status {status[:n].cpu().numpy().tolist()[:8]})")
-    return TypeCodes(codes=codes, l1=l1, m=msgs.m, overflow=kmax)
+    return TypeCodes(codes=codes, l1=l1, m=msgs.m, overflow=kmax, form=msgs.form)

@@ -22,8 +22,8 @@ std::atomic<int> g_force_replay_failure{0};
 constexpr int64_t kCandMultiMaxN = 16;
 
 // ---- dispatch plan -------------------------------------------------------------------
-// Every decision of a call, made once on the host from (n, d, tie_policy, alignment of x and
-// out); DESIGN.md §4.2 has the table.  The launchers launch what the plan names and the
+// Every decision of a call, made once on the host from (n, d, tie_policy, alignment of x, out
+// and, in a codes call, the codes rows); DESIGN.md §4.2 has the table.  The launchers launch what the plan names and the
 // workspace layout reads its sizes, so the test hooks (uq_test_biased_plan,
 // uq_test_last_biased_plan) report what a call really runs.
 struct BiasedPlan {
@@ -31,7 +31,7 @@ struct BiasedPlan {
     int32_t ties = UQ_BIASED_TIES_LOWEST;   // the tail after the selection (small-checked: if a row is ambiguous)
     int32_t levels = 0, lsplit = 0;         // KB7a's levels, lsplit of them before KB6; 0: one rez_ties_kernel launch
     uint32_t lgrid = 0;                     // workgroups of KB7a's per-level launches
-    bool vec4 = false;                      // 16-byte accesses to x and out
+    bool vec4 = false;                      // 16-byte accesses to x and out, 4-byte ones to the codes
     bool cand_multi = false;                // KB4d over cspans workgroups per client
     bool clear_bits = false;                // a memset clears the tie bits (KB7a's level-0 kt_count does it otherwise)
     uint32_t cspans = 0;
@@ -55,7 +55,10 @@ int biased_check(int64_t n, int64_t d, int64_t m, int32_t T, int32_t tie_policy)
     return UQ_OK;
 }
 
-BiasedPlan biased_plan(int64_t n, int64_t d, int32_t tie_policy, bool x_aligned, bool out_aligned) {
+// out_aligned: true where a codes call writes no out; codes_aligned: the codes rows start on
+// 4-byte boundaries (true where the call writes no codes)
+BiasedPlan biased_plan(int64_t n, int64_t d, int32_t tie_policy, bool x_aligned, bool out_aligned,
+                       bool codes_aligned = true) {
     BiasedPlan p;
     p.tiles = (int32_t)((d + kSelTile - 1) / kSelTile);
     p.slots = (int32_t)std::min<int64_t>(n, kTieSlots);
@@ -70,7 +73,7 @@ BiasedPlan biased_plan(int64_t n, int64_t d, int32_t tie_policy, bool x_aligned,
     // multi-kernel path when a threshold tie needs torch's choice
     const bool small = d <= kSmallBiasedMax && (!torch || (host_check && n <= kSmallCheckMaxN));
     p.front = !small ? UQ_BIASED_FRONT_FULL : torch ? UQ_BIASED_FRONT_SMALL_CHECKED : UQ_BIASED_FRONT_SMALL;
-    p.vec4 = x_aligned && out_aligned && d % 4 == 0;
+    p.vec4 = x_aligned && out_aligned && codes_aligned && d % 4 == 0;
     p.cand_multi = n <= kCandMultiMaxN && p.cspans > 1;
     if (!torch) return p;
     // KB7a pays ~85 short launches whether or not any client is listed (the host does not
@@ -112,12 +115,14 @@ int export_plan(const BiasedPlan& p, int64_t* out, int32_t cap) {
 // [hist n x 3 x 2048 u32][zero/NaN counts n x 2][candidate counts n][candidates n x cap u32]
 // [tie counts n x tiles u32][tie bits n x ceil(d/32) u32]
 // [KB7 slots: keys + indices S x 2d u32][KB7 positions S x 2d u32], S = the plan's slots
+// ... [codes calls: the largest coded count per output tile, n x tiles i32]
 struct BiasedLayout {
     size_t part_off, l1_off, msum_off, st_off, hist_off, zn_off, cn_off, fl_off, cand_off, tcnt_off, bits_off,
-        pairs_off, pos_off, list_off, tls_off, tcnt2_off, alist_off, total;
+        pairs_off, pos_off, list_off, tls_off, tcnt2_off, alist_off, kmt_off, total;
 };
 
-BiasedLayout biased_layout(int64_t n, int64_t d, const L1Plan& plan, const BiasedPlan& P) {
+// codes: the layout of a codes call (uq_biased_codes_workspace_bytes), with the tile maxima at the end
+BiasedLayout biased_layout(int64_t n, int64_t d, const L1Plan& plan, const BiasedPlan& P, bool codes = false) {
     BiasedLayout w{};
     w.part_off = kCtrlBytes;
     w.l1_off = up256(w.part_off + (size_t)n * plan.total_groups * 32 * sizeof(float));
@@ -136,7 +141,8 @@ BiasedLayout biased_layout(int64_t n, int64_t d, const L1Plan& plan, const Biase
     w.tls_off = up256(w.list_off + (size_t)(n + 1) * sizeof(uint32_t));    // KB7's client list
     w.tcnt2_off = up256(w.tls_off + (size_t)P.slots * sizeof(TieLevelState));
     w.alist_off = up256(w.tcnt2_off + (size_t)P.slots * kTieSegs * 2 * sizeof(uint32_t));
-    w.total = up256(w.alist_off + (size_t)(kTieSlots + 1) * sizeof(uint32_t));    // KB7a's active slots
+    w.kmt_off = up256(w.alist_off + (size_t)(kTieSlots + 1) * sizeof(uint32_t));    // KB7a's active slots
+    w.total = codes ? up256(w.kmt_off + (size_t)n * P.tiles * sizeof(int32_t)) : w.kmt_off;
     return w;
 }
 
@@ -150,6 +156,9 @@ struct BiasedCall {
     const BiasedLayout& w;
     char* wsb;
     hipStream_t st;                     // the caller's stream
+    int8_t* codes = nullptr;            // a codes call (uq_type_biased_codes_f32): the codes [n][d] and kmax [n];
+    int32_t* kmax = nullptr;            // out may then be null (codes only)
+    int32_t* kmt = (int32_t*)(wsb + w.kmt_off);         // the writers' per-tile maxima, folded into kmax at the end
     float* l1buf = (float*)(wsb + w.l1_off);
     RezState* state = (RezState*)(wsb + w.st_off);
     uint32_t* hist = (uint32_t*)(wsb + w.hist_off);
@@ -172,6 +181,14 @@ template <class F>
 void select_vec4(bool vec4, F&& f) {
     if (vec4) f(Flag<true>{});
     else f(Flag<false>{});
+}
+// f(CM) for the codes mode of a codes call: kOutCodes, or kCodesOnly without out.
+template <int M>
+using Mode = std::integral_constant<int, M>;
+template <class F>
+void select_codes(const float* out, F&& f) {
+    if (out) f(Mode<kOutCodes>{});
+    else f(Mode<kCodesOnly>{});
 }
 template <class F>
 void each_digit(F&& f) {
@@ -324,6 +341,21 @@ int launch_small(const BiasedCall& c) {
                                   (int)(kSmallBiasedMax * sizeof(uint32_t)));
         attr_set.fetch_or(1ull << dev);
     }
+    if (c.codes) {
+        static std::atomic<uint64_t> cattr_set{0};            // per device, both codes instances
+        if (dev >= 0 && dev < 64 && !((cattr_set.load() >> dev) & 1u)) {
+            (void)hipFuncSetAttribute((const void*)biased_small_codes_kernel<kOutCodes>,
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kSmallBiasedMax * sizeof(uint32_t)));
+            (void)hipFuncSetAttribute((const void*)biased_small_codes_kernel<kCodesOnly>,
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kSmallBiasedMax * sizeof(uint32_t)));
+            cattr_set.fetch_or(1ull << dev);
+        }
+        select_codes(c.out, [&](auto CM) {
+            hipLaunchKernelGGL(biased_small_codes_kernel<CM()>, dim3((unsigned)c.n), dim3(256), (size_t)c.d * sizeof(uint32_t),
+                               c.st, c.x, c.out, c.d, c.fm, (const float*)nullptr, c.l1buf, c.state, c.codes, c.kmt, c.P.tiles);
+        });
+        return launched("biased_small_codes_kernel launch");
+    }
     hipLaunchKernelGGL(biased_small_kernel, dim3((unsigned)c.n), dim3(256), (size_t)c.d * sizeof(uint32_t), c.st, c.x, c.out,
                        c.d, c.fm, (const float*)nullptr, c.l1buf, c.state);
     return launched("biased_small_kernel launch");
@@ -376,8 +408,14 @@ int launch_select(const BiasedCall& c, int32_t T, const L1Plan& plan) {
     // fine clients: KB6f writes every output and lists the bucket, KB4d finds the threshold
     // key among the listed keys, KB6p patches the selected listed coordinates (tie-free clients)
     select_vec4(P.vec4, [&](auto V4) {
-        hipLaunchKernelGGL(rez_output_fine_kernel<V4()>, dim3((unsigned)P.tiles, (unsigned)n), dim3(256), 0, c.st, c.x, c.out, d,
-                           c.l1buf, c.fm, c.state, c.fcand, c.cand_n, P.capf);
+        if (c.codes)
+            select_codes(c.out, [&](auto CM) {
+                hipLaunchKernelGGL((rez_output_fine_codes_kernel<V4(), CM()>), dim3((unsigned)P.tiles, (unsigned)n), dim3(256), 0,
+                                   c.st, c.x, c.out, d, c.l1buf, c.fm, c.state, c.fcand, c.cand_n, P.capf, c.codes, c.kmt);
+            });
+        else
+            hipLaunchKernelGGL(rez_output_fine_kernel<V4()>, dim3((unsigned)P.tiles, (unsigned)n), dim3(256), 0, c.st, c.x, c.out, d,
+                               c.l1buf, c.fm, c.state, c.fcand, c.cand_n, P.capf);
     });
     if (P.cand_multi) {                          // few clients: the passes over many workgroups
         each_digit([&](auto D) {
@@ -394,8 +432,14 @@ int launch_select(const BiasedCall& c, int32_t T, const L1Plan& plan) {
 // KB6p: the tie-free fine clients' selected bin coordinates (independent of KB7: with the
 // torch-tie fork it runs on the caller's stream beside the replay chain, off its path)
 int launch_fine_patch(const BiasedCall& c) {
-    hipLaunchKernelGGL(rez_fine_patch_kernel, dim3(kPatchBlocks, (unsigned)c.n), dim3(256), 0, c.st, c.x, c.out, c.d, c.l1buf,
-                       c.fm, c.state, c.fcand, c.cand_n, c.P.capf);
+    if (c.codes)
+        select_codes(c.out, [&](auto CM) {
+            hipLaunchKernelGGL(rez_fine_patch_codes_kernel<CM()>, dim3(kPatchBlocks, (unsigned)c.n), dim3(256), 0, c.st, c.x,
+                               c.out, c.d, c.l1buf, c.fm, c.state, c.fcand, c.cand_n, c.P.capf, c.codes, c.kmt, c.P.tiles);
+        });
+    else
+        hipLaunchKernelGGL(rez_fine_patch_kernel, dim3(kPatchBlocks, (unsigned)c.n), dim3(256), 0, c.st, c.x, c.out, c.d, c.l1buf,
+                           c.fm, c.state, c.fcand, c.cand_n, c.P.capf);
     return launched("rez_fine_patch_kernel launch");
 }
 
@@ -408,8 +452,14 @@ int launch_fine_patch(const BiasedCall& c) {
 int launch_output(const BiasedCall& c, int part, const uint32_t* ol) {
     const dim3 ogrid((unsigned)c.P.tiles, ol ? c.listed_y : (unsigned)c.n);
     select_vec4(c.P.vec4, [&](auto V4) {
-        hipLaunchKernelGGL(rez_output_kernel<V4()>, ogrid, dim3(256), 0, c.st, c.x, c.out, c.d, c.l1buf, c.fm, c.state, c.tcnt,
-                           c.P.tiles, c.bits, part, ol);
+        if (c.codes)
+            select_codes(c.out, [&](auto CM) {
+                hipLaunchKernelGGL((rez_output_codes_kernel<V4(), CM()>), ogrid, dim3(256), 0, c.st, c.x, c.out, c.d, c.l1buf,
+                                   c.fm, c.state, c.tcnt, c.P.tiles, c.bits, part, ol, c.codes, c.kmt);
+            });
+        else
+            hipLaunchKernelGGL(rez_output_kernel<V4()>, ogrid, dim3(256), 0, c.st, c.x, c.out, c.d, c.l1buf, c.fm, c.state, c.tcnt,
+                               c.P.tiles, c.bits, part, ol);
     });
     return launched("rez_output_kernel launch");
 }
@@ -420,8 +470,14 @@ int launch_output(const BiasedCall& c, int part, const uint32_t* ol) {
 int launch_output_listed(const BiasedCall& c) {
     const int rc = launch_output(c, 2, c.list);
     if (rc) return rc;
-    hipLaunchKernelGGL(rez_tie_patch_kernel, dim3(kPatchBlocks, c.listed_y), dim3(256), 0, c.st, c.x, c.out, c.d, c.l1buf,
-                       c.fm, c.state, c.fcand, c.cand_n, c.P.capf, c.bits, c.list);
+    if (c.codes)
+        select_codes(c.out, [&](auto CM) {
+            hipLaunchKernelGGL(rez_tie_patch_codes_kernel<CM()>, dim3(kPatchBlocks, c.listed_y), dim3(256), 0, c.st, c.x, c.out,
+                               c.d, c.l1buf, c.fm, c.state, c.fcand, c.cand_n, c.P.capf, c.bits, c.list, c.codes, c.kmt, c.P.tiles);
+        });
+    else
+        hipLaunchKernelGGL(rez_tie_patch_kernel, dim3(kPatchBlocks, c.listed_y), dim3(256), 0, c.st, c.x, c.out, c.d, c.l1buf,
+                           c.fm, c.state, c.fcand, c.cand_n, c.P.capf, c.bits, c.list);
     return launched("rez_tie_patch_kernel launch");
 }
 
@@ -485,6 +541,9 @@ int tail_fork(const BiasedCall& c) {
     return launch_output_listed(c);
 }
 
+int biased_impl(const float* x, float* out, int8_t* codes, int32_t* kmax, int64_t n, int64_t d, int64_t m, int32_t T,
+                int32_t tie_policy, float* l1_out, int32_t* info, void* ws, size_t ws_bytes, void* stream);
+
 }  // namespace
 
 extern "C" {
@@ -508,16 +567,50 @@ int uq_biased_workspace_bytes(int64_t n, int64_t d, int32_t T, size_t* bytes_out
     return UQ_OK;
 }
 
+int uq_biased_codes_workspace_bytes(int64_t n, int64_t d, int32_t T, size_t* bytes_out) {
+    if (!bytes_out) return fail(UQ_E_INVALID, "null bytes_out");
+    L1Plan plan;
+    if (n < 0 || d < 0 || T < 1) return fail(UQ_E_INVALID, "bad n/d/torch_threads");
+    if (!make_plan(d, T, &plan)) return fail(UQ_E_INVALID, "cannot build L1 plan");
+    *bytes_out = biased_layout(n, d, plan, biased_plan(n, d, UQ_TIES_TORCH, false, false), true).total;
+    return UQ_OK;
+}
+
 int uq_type_biased_f32(const float* x, float* out, int64_t n, int64_t d, int64_t m, int32_t T,
                        int32_t tie_policy, float* l1_out, int32_t* info, void* ws, size_t ws_bytes,
                        void* stream) {
+    return biased_impl(x, out, nullptr, nullptr, n, d, m, T, tie_policy, l1_out, info, ws, ws_bytes, stream);
+}
+
+int uq_type_biased_codes_f32(const float* x, float* out, int8_t* codes, int32_t* kmax, int64_t n, int64_t d, int64_t m,
+                             int32_t T, int32_t tie_policy, float* l1_out, int32_t* info, void* ws, size_t ws_bytes,
+                             void* stream) {
+    t_last_plan = BiasedPlan{};
+    const int rc = biased_check(n, d, m, T, tie_policy);
+    if (rc) return rc;
+    if (m < 1) return fail(UQ_E_INVALID, "m must be >= 1 for type codes");
+    if (n == 0 || d == 0) return UQ_OK;
+    if (!codes || !kmax) return fail(UQ_E_INVALID, "null codes or kmax");
+    if (!l1_out) return fail(UQ_E_INVALID, "null l1_out (the codes are decoded with it)");
+    return biased_impl(x, out, codes, kmax, n, d, m, T, tie_policy, l1_out, info, ws, ws_bytes, stream);
+}
+
+}  // extern "C"
+
+namespace {
+
+// uq_type_biased_f32 (codes null), and uq_type_biased_codes_f32 after its own checks (codes and
+// kmax given, out may be null).
+int biased_impl(const float* x, float* out, int8_t* codes, int32_t* kmax, int64_t n, int64_t d, int64_t m, int32_t T,
+                int32_t tie_policy, float* l1_out, int32_t* info, void* ws, size_t ws_bytes, void* stream) {
     t_last_plan = BiasedPlan{};
     int rc = biased_check(n, d, m, T, tie_policy);
     if (rc) return rc;
     L1Plan plan;
     if (!make_plan(d, T, &plan)) return fail(UQ_E_INVALID, "cannot build L1 plan for this d/torch_threads");
-    const BiasedPlan P = biased_plan(n, d, tie_policy, aligned16(x), aligned16(out));
-    const BiasedLayout w = biased_layout(n, d, plan, P);
+    const BiasedPlan P = biased_plan(n, d, tie_policy, aligned16(x), !out || aligned16(out),
+                                     ((uintptr_t)codes & 3u) == 0);
+    const BiasedLayout w = biased_layout(n, d, plan, P, codes != nullptr);
     if (n == 0) return UQ_OK;
     hipStream_t st = (hipStream_t)stream;
     if (d == 0) {
@@ -525,13 +618,23 @@ int uq_type_biased_f32(const float* x, float* out, int64_t n, int64_t d, int64_t
         if (!rc && info) rc = hip_check(hipMemsetAsync(info, 0, n * 2 * sizeof(int32_t), st), "memset info");
         return rc;
     }
-    if (!x || !out) return fail(UQ_E_INVALID, "null x or out");
+    if (!x || (!out && !codes)) return fail(UQ_E_INVALID, "null x or out");
     if (!ws) return fail(UQ_E_INVALID, "null workspace");
     if (ws_bytes < w.total) return fail(UQ_E_WORKSPACE, "workspace too small");
     t_last_plan = P;
-    const BiasedCall c{x, out, n, d, (float)m, P, w, (char*)ws, st};
-    auto finish = [&]() {                     // l1_out and the info pairs
+    const BiasedCall c{x, out, n, d, (float)m, P, w, (char*)ws, st, codes, kmax};
+    auto clear_kmax = [&]() {                 // the per-tile maxima: the writers raise them with atomicMax
+        return codes ? hip_check(hipMemsetAsync(c.kmt, 0, (size_t)n * P.tiles * sizeof(int32_t), st), "memset tile kmax")
+                     : (int)UQ_OK;
+    };
+    if ((rc = clear_kmax())) return rc;
+    auto finish = [&]() {                     // kmax's flagged rows, l1_out and the info pairs
         int frc = UQ_OK;
+        if (codes) {
+            hipLaunchKernelGGL(rez_kmax_finish_kernel, dim3((unsigned)n), dim3(256), 0, st, kmax, c.kmt, P.tiles, c.l1buf,
+                               c.state);
+            if ((frc = launched("rez_kmax_finish_kernel launch"))) return frc;
+        }
         if (l1_out) frc = hip_check(hipMemcpyAsync(l1_out, c.l1buf, n * sizeof(float), hipMemcpyDeviceToDevice, st), "copy l1");
         if (!frc && info)
             frc = hip_check(hipMemcpy2DAsync(info, 2 * sizeof(int32_t), c.state, sizeof(RezState), 2 * sizeof(int32_t), n,
@@ -542,6 +645,7 @@ int uq_type_biased_f32(const float* x, float* out, int64_t n, int64_t d, int64_t
         if ((rc = launch_small(c))) return rc;
         if (P.front == UQ_BIASED_FRONT_SMALL_CHECKED && (rc = small_has_tie(c, &t_last_plan.ran))) return rc;
         if (t_last_plan.ran <= 0) return finish();       // the lowest-index rule, or no ambiguous row
+        if ((rc = clear_kmax())) return rc;              // the multi-kernel path writes every row again
     }
     if ((rc = launch_select(c, T, plan))) return rc;
     if (P.ties == UQ_BIASED_TIES_LOWEST) rc = tail_lowest(c);
@@ -550,4 +654,4 @@ int uq_type_biased_f32(const float* x, float* out, int64_t n, int64_t d, int64_t
     return rc ? rc : finish();
 }
 
-}  // extern "C"
+}  // namespace

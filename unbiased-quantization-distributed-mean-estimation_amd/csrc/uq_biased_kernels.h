@@ -561,13 +561,72 @@ __device__ __forceinline__ float torch_signf(float v) {
     return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f);
 }
 
+// ---- type codes of the biased type (uq_type_biased_codes_f32) --------------------------
+// Every writer of `out` has instances that also (kOutCodes) or only (kCodesOnly) write the int8
+// code of the same k'': k'' for x > 0, -k''-1 for x < 0, 0 for x == 0 (sign 0: the output is
+// +0.0 whatever k'').  kOutOnly is the code uq_type_biased_f32 has always launched.
+enum CodesMode : int { kOutOnly = 0, kOutCodes = 1, kCodesOnly = 2 };
+
+// The code of one coordinate and the running maximum `km` of the coded counts: 128 once a
+// count does not fit (above 127, saturated; negative or NaN cannot be coded either).
+__device__ __forceinline__ int rez_code(float xv, float kq, int& km) {
+    const int kc = (int)fminf(fmaxf(kq, -1.0f), 128.0f);       // (NaN -> -1)
+    const int k = min(max(kc, 0), 127);
+    const bool pos = xv > 0.f, neg = xv < 0.f;
+    km = max(km, (kc < 0 || kc > 127) ? 128 : ((pos || neg) ? k : 0));
+    return pos ? k : (neg ? ~k : 0);
+}
+
+// Four codes as one 32-bit word (coordinate c in byte c).
+__device__ __forceinline__ uint32_t rez_code4(const float (&xv)[4], const float (&kq)[4], int& km) {
+    uint32_t w = 0u;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) w |= ((uint32_t)rez_code(xv[c], kq[c], km) & 0xFFu) << (8 * c);
+    return w;
+}
+
+// The largest coded count per client is gathered per output tile: kmt[vec * tiles + tile]
+// (workspace, zeroed by the call) takes an atomicMax from each wave that coded a count > 0, and
+// rez_kmax_finish_kernel folds a client's tiles into kmax[vec].  (One word per client instead had
+// every wave of a client, 4 d / 4096 of them, queue on one address: KB6f with both outputs took 2.26 ms for 1.91.)
+// Called by every thread of the workgroup.
+__device__ __forceinline__ void rez_publish_kmax(int km, int32_t* __restrict__ kmt, int64_t slot) {
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) km = max(km, __shfl_xor(km, o, kWave));
+    if ((threadIdx.x & (kWave - 1)) == 0 && km > 0) atomicMax(&kmt[slot], km);
+}
+
+// kmax[vec] = the largest of the client's tile maxima, or 128 for a client whose codes must not
+// be decoded (a count that did not fit at any stage, L1 not finite, m' not finite, |Delta| > d).
+// One workgroup per client.
+__global__ void __launch_bounds__(256)
+rez_kmax_finish_kernel(int32_t* __restrict__ kmaxv, const int32_t* __restrict__ kmt, int32_t tiles,
+                       const float* __restrict__ l1, const RezState* __restrict__ st) {
+    __shared__ int s_km;
+    const int64_t vec = blockIdx.x;
+    if (threadIdx.x == 0) s_km = 0;
+    __syncthreads();
+    int km = 0;
+    for (int32_t t = threadIdx.x; t < tiles; t += 256) km = max(km, kmt[vec * tiles + t]);
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) km = max(km, __shfl_xor(km, o, kWave));
+    if ((threadIdx.x & (kWave - 1)) == 0) atomicMax(&s_km, km);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const bool bad = !isfinite(l1[vec]) || (st[vec].flags & (kRezNonFinite | kRezRange)) || s_km > 127;
+        kmaxv[vec] = bad ? 128 : s_km;
+    }
+}
+
 // KB6: apply the selection and dequantize.  Selected = key > tau, or key == tau and
 // (all ties are selected | rank among ties in index order < need | marked by KB7).
-template <bool VEC4>
+template <bool VEC4, int CM = kOutOnly>
 __device__ __forceinline__ void rez_output_tile(const float* __restrict__ x, float* __restrict__ out, int64_t d,
                                                 const float* __restrict__ l1, float fm, const RezState* __restrict__ st,
                                                 const uint32_t* __restrict__ tilecnt, int32_t tiles,
-                                                const uint32_t* __restrict__ tie_bits, int part, int64_t vec) {
+                                                const uint32_t* __restrict__ tie_bits, int part, int64_t vec,
+                                                int8_t* __restrict__ codes = nullptr,
+                                                int32_t* __restrict__ kmt = nullptr) {
     const RezState s = st[vec];
     const bool on = s.kleft != 0;
     const bool amb = on && (s.flags & kRezAmbiguous);
@@ -590,6 +649,8 @@ __device__ __forceinline__ void rez_output_tile(const float* __restrict__ x, flo
     const uint32_t tau = s.prefix;
     const float* xv = x + vec * d;
     float* ov = out + vec * d;
+    int8_t* cvr = codes + vec * d;
+    int km = 0;
     const int tid = threadIdx.x;
     const int64_t tb = (int64_t)blockIdx.x * kSelTile;
     if (VEC4 && !(amb && !replay) && tb + kSelTile <= d) {
@@ -618,14 +679,19 @@ __device__ __forceinline__ void rez_output_tile(const float* __restrict__ x, flo
                 }
                 k4[c] = sel ? k4[c] + adj : k4[c];             // k''
             }
-            div4(k4, dpm, r4);                                 // RN(k'' / m)
-            f4v o;
-            o.x = (L * torch_signf(v4[0])) * r4[0];            // AS:687 (L1 * signs) * (k'' / m)
-            o.y = (L * torch_signf(v4[1])) * r4[1];
-            o.z = (L * torch_signf(v4[2])) * r4[2];
-            o.w = (L * torch_signf(v4[3])) * r4[3];
-            __builtin_nontemporal_store(o, o4 + j * 256 + tid);
+            if constexpr (CM != kOutOnly)                      // the four codes: one 32-bit word
+                __builtin_nontemporal_store(rez_code4(v4, k4, km), reinterpret_cast<uint32_t*>(cvr + tb) + j * 256 + tid);
+            if constexpr (CM != kCodesOnly) {
+                div4(k4, dpm, r4);                                 // RN(k'' / m)
+                f4v o;
+                o.x = (L * torch_signf(v4[0])) * r4[0];            // AS:687 (L1 * signs) * (k'' / m)
+                o.y = (L * torch_signf(v4[1])) * r4[1];
+                o.z = (L * torch_signf(v4[2])) * r4[2];
+                o.w = (L * torch_signf(v4[3])) * r4[3];
+                __builtin_nontemporal_store(o, o4 + j * 256 + tid);
+            }
         }
+        if constexpr (CM != kOutOnly) rez_publish_kmax(km, kmt, vec * tiles + blockIdx.x);
         return;
     }
     const int64_t e0 = tb + (int64_t)tid * kSelItems;
@@ -689,6 +755,23 @@ __device__ __forceinline__ void rez_output_tile(const float* __restrict__ x, flo
         }
         q[j] = sel ? kp[j] + adj : kp[j];                 // k''
     }
+    if constexpr (CM != kOutOnly) {
+#pragma unroll
+        for (int j = 0; j < kSelItems / 4; ++j) {
+            const float v4[4] = {v[4 * j], v[4 * j + 1], v[4 * j + 2], v[4 * j + 3]};
+            const float k4[4] = {q[4 * j], q[4 * j + 1], q[4 * j + 2], q[4 * j + 3]};
+            const uint32_t w = rez_code4(v4, k4, km);          // (coordinates past d: x = 0, code 0)
+            if (full) {
+                reinterpret_cast<uint32_t*>(cvr + e0)[j] = w;
+            } else {
+#pragma unroll
+                for (int c = 0; c < 4; ++c)
+                    if (e0 + 4 * j + c < d) cvr[e0 + 4 * j + c] = (int8_t)(w >> (8 * c));
+            }
+        }
+        rez_publish_kmax(km, kmt, vec * tiles + blockIdx.x);
+        if constexpr (CM == kCodesOnly) return;
+    }
 #pragma unroll
     for (int j = 0; j < kSelItems / 4; ++j) {
         const float k4[4] = {q[4 * j], q[4 * j + 1], q[4 * j + 2], q[4 * j + 3]};
@@ -727,6 +810,24 @@ rez_output_kernel(const float* __restrict__ x, float* __restrict__ out, int64_t 
     }
 }
 
+// KB6 with the codes (CM: kOutCodes or kCodesOnly, out null), the same grids as rez_output_kernel.
+template <bool VEC4, int CM>
+__global__ void __launch_bounds__(256)
+rez_output_codes_kernel(const float* __restrict__ x, float* __restrict__ out, int64_t d, const float* __restrict__ l1,
+                        float fm, const RezState* __restrict__ st, const uint32_t* __restrict__ tilecnt, int32_t tiles,
+                        const uint32_t* __restrict__ tie_bits, int part, const uint32_t* __restrict__ list,
+                        int8_t* __restrict__ codes, int32_t* __restrict__ kmt) {
+    if (!list) {
+        rez_output_tile<VEC4, CM>(x, out, d, l1, fm, st, tilecnt, tiles, tie_bits, part, blockIdx.y, codes, kmt);
+        return;
+    }
+    const uint32_t nl = list[0];
+    for (uint32_t li = blockIdx.y; li < nl; li += gridDim.y) {
+        rez_output_tile<VEC4, CM>(x, out, d, l1, fm, st, tilecnt, tiles, tie_bits, part, list[1 + li], codes, kmt);
+        __syncthreads();                               // the rank scans' LDS, reused by the next client
+    }
+}
+
 // KB6f: fine clients (kRezFine) -- out for every coordinate with the selection decided by the
 // fine bin (above the threshold's bin: selected; below: not); the threshold bin's coordinates
 // are written unselected and listed as (index, key) pairs for KB4d: staged in LDS by LDS
@@ -735,11 +836,12 @@ rez_output_kernel(const float* __restrict__ x, float* __restrict__ out, int64_t 
 // 0.01-0.05 ms faster, profiles/r5p_exp_biased_kb6f_lds.jsonl).  The same arithmetic as KB6, so
 // KB6p's patch gives KB6's bits.
 constexpr uint32_t kFineStage = 256;
-template <bool VEC4>
-__global__ void __launch_bounds__(256)
-rez_output_fine_kernel(const float* __restrict__ x, float* __restrict__ out, int64_t d, const float* __restrict__ l1,
-                       float fm, const RezState* __restrict__ st, uint2* __restrict__ cand,
-                       uint32_t* __restrict__ cand_n, uint32_t capf) {
+template <bool VEC4, int CM>
+__device__ __forceinline__ void rez_output_fine_body(const float* __restrict__ x, float* __restrict__ out, int64_t d,
+                                                     const float* __restrict__ l1, float fm,
+                                                     const RezState* __restrict__ st, uint2* __restrict__ cand,
+                                                     uint32_t* __restrict__ cand_n, uint32_t capf,
+                                                     int8_t* __restrict__ codes, int32_t* __restrict__ kmt) {
     const int64_t vec = blockIdx.y;
     const RezState s = st[vec];
     if (s.kleft == 0 || !(s.flags & kRezFine)) return;
@@ -751,6 +853,8 @@ rez_output_fine_kernel(const float* __restrict__ x, float* __restrict__ out, int
     const uint32_t fb = s.fbin;
     const float* xv = x + vec * d;
     float* ov = out + vec * d;
+    int8_t* cvr = codes + vec * d;
+    int km = 0;
     const int tid = threadIdx.x;
     const int64_t tb = (int64_t)blockIdx.x * kSelTile;
     // past kFineStage pairs (tie-heavy tiles), straight to the global list
@@ -788,13 +892,17 @@ rez_output_fine_kernel(const float* __restrict__ x, float* __restrict__ out, int
             const int64_t i0 = tb + 4 * ((int64_t)j * 256 + tid);
 #pragma unroll
             for (int c = 0; c < 4; ++c) one(v4[c], k4[c], y4[c], i0 + c, q4[c]);
-            div4(q4, dpm, r4);                                 // RN(k'' / m)
-            f4v o;
-            o.x = (L * torch_signf(v4[0])) * r4[0];            // AS:687 (L1 * signs) * (k'' / m)
-            o.y = (L * torch_signf(v4[1])) * r4[1];
-            o.z = (L * torch_signf(v4[2])) * r4[2];
-            o.w = (L * torch_signf(v4[3])) * r4[3];
-            __builtin_nontemporal_store(o, o4 + j * 256 + tid);
+            if constexpr (CM != kOutOnly)                      // the four codes: one 32-bit word
+                __builtin_nontemporal_store(rez_code4(v4, q4, km), reinterpret_cast<uint32_t*>(cvr + tb) + j * 256 + tid);
+            if constexpr (CM != kCodesOnly) {
+                div4(q4, dpm, r4);                                 // RN(k'' / m)
+                f4v o;
+                o.x = (L * torch_signf(v4[0])) * r4[0];            // AS:687 (L1 * signs) * (k'' / m)
+                o.y = (L * torch_signf(v4[1])) * r4[1];
+                o.z = (L * torch_signf(v4[2])) * r4[2];
+                o.w = (L * torch_signf(v4[3])) * r4[3];
+                __builtin_nontemporal_store(o, o4 + j * 256 + tid);
+            }
         }
     } else {
         const int64_t e0 = tb + (int64_t)tid * kSelItems;
@@ -811,12 +919,21 @@ rez_output_fine_kernel(const float* __restrict__ x, float* __restrict__ out, int
                 if (e0 + 4 * j + c < d) one(v4[c], k4[c], y4[c], e0 + 4 * j + c, q4[c]);
                 else q4[c] = 0.f;
             }
-            div4(q4, dpm, r4);
+            if constexpr (CM != kOutOnly) {
+                const uint32_t w = rez_code4(v4, q4, km);      // (coordinates past d: x = 0, code 0)
 #pragma unroll
-            for (int c = 0; c < 4; ++c)
-                if (e0 + 4 * j + c < d) ov[e0 + 4 * j + c] = (L * torch_signf(v4[c])) * r4[c];
+                for (int c = 0; c < 4; ++c)
+                    if (e0 + 4 * j + c < d) cvr[e0 + 4 * j + c] = (int8_t)(w >> (8 * c));
+            }
+            if constexpr (CM != kCodesOnly) {
+                div4(q4, dpm, r4);
+#pragma unroll
+                for (int c = 0; c < 4; ++c)
+                    if (e0 + 4 * j + c < d) ov[e0 + 4 * j + c] = (L * torch_signf(v4[c])) * r4[c];
+            }
         }
     }
+    if constexpr (CM != kOutOnly) rez_publish_kmax(km, kmt, vec * gridDim.x + blockIdx.x);   // (grid x: the tiles)
     __syncthreads();
     const uint32_t tot = min(s_cnt, (uint32_t)kFineStage);
     if (tot == 0) return;                                      // block-uniform
@@ -827,14 +944,35 @@ rez_output_fine_kernel(const float* __restrict__ x, float* __restrict__ out, int
         if (s_base + t < capf) cv[s_base + t] = stage[t];
 }
 
+template <bool VEC4>
+__global__ void __launch_bounds__(256)
+rez_output_fine_kernel(const float* __restrict__ x, float* __restrict__ out, int64_t d, const float* __restrict__ l1,
+                       float fm, const RezState* __restrict__ st, uint2* __restrict__ cand,
+                       uint32_t* __restrict__ cand_n, uint32_t capf) {
+    rez_output_fine_body<VEC4, kOutOnly>(x, out, d, l1, fm, st, cand, cand_n, capf, nullptr, nullptr);
+}
+
+// KB6f with the codes (CM: kOutCodes or kCodesOnly, out null).
+template <bool VEC4, int CM>
+__global__ void __launch_bounds__(256)
+rez_output_fine_codes_kernel(const float* __restrict__ x, float* __restrict__ out, int64_t d,
+                             const float* __restrict__ l1, float fm, const RezState* __restrict__ st,
+                             uint2* __restrict__ cand, uint32_t* __restrict__ cand_n, uint32_t capf,
+                             int8_t* __restrict__ codes, int32_t* __restrict__ kmt) {
+    rez_output_fine_body<VEC4, CM>(x, out, d, l1, fm, st, cand, cand_n, capf, codes, kmt);
+}
+
 // KB6p: the listed coordinates of a fine client without a threshold tie that are selected
 // (key >= the threshold key: every tie is selected) get k'' = k' -+ 1.
 constexpr int kPatchBlocks = 4;
 constexpr int64_t kListedGridY = 64;      // list-strided launches after KB7: y extent
-__global__ void __launch_bounds__(256)
-rez_fine_patch_kernel(const float* __restrict__ x, float* __restrict__ out, int64_t d, const float* __restrict__ l1,
-                      float fm, const RezState* __restrict__ st, const uint2* __restrict__ cand,
-                      const uint32_t* __restrict__ cand_n, uint32_t capf) {
+template <int CM>
+__device__ __forceinline__ void rez_fine_patch_body(const float* __restrict__ x, float* __restrict__ out, int64_t d,
+                                                    const float* __restrict__ l1, float fm,
+                                                    const RezState* __restrict__ st, const uint2* __restrict__ cand,
+                                                    const uint32_t* __restrict__ cand_n, uint32_t capf,
+                                                    int8_t* __restrict__ codes, int32_t* __restrict__ kmt,
+                                                    int32_t tiles) {
     const int64_t vec = blockIdx.y;
     const RezState s = st[vec];
     if (s.kleft == 0 || !(s.flags & kRezFine) || (s.flags & kRezAmbiguous)) return;
@@ -851,19 +989,45 @@ rez_fine_patch_kernel(const float* __restrict__ x, float* __restrict__ out, int6
         const float v = x[vec * d + c.x];
         float kp;
         (void)rez_elem(v, dp, fm, up, kp);
-        out[vec * d + c.x] = (L * torch_signf(v)) * div1(kp + adj, dpm);     // AS:687 with k''
+        if constexpr (CM != kOutOnly) {                        // (a few listed coordinates per thread)
+            int km = 0;
+            codes[vec * d + c.x] = (int8_t)rez_code(v, kp + adj, km);
+            if (km > 0) atomicMax(&kmt[vec * tiles + c.x / kSelTile], km);
+        }
+        if constexpr (CM != kCodesOnly)
+            out[vec * d + c.x] = (L * torch_signf(v)) * div1(kp + adj, dpm);     // AS:687 with k''
     }
+}
+
+__global__ void __launch_bounds__(256)
+rez_fine_patch_kernel(const float* __restrict__ x, float* __restrict__ out, int64_t d, const float* __restrict__ l1,
+                      float fm, const RezState* __restrict__ st, const uint2* __restrict__ cand,
+                      const uint32_t* __restrict__ cand_n, uint32_t capf) {
+    rez_fine_patch_body<kOutOnly>(x, out, d, l1, fm, st, cand, cand_n, capf, nullptr, nullptr, 0);
+}
+
+// KB6p with the codes (CM: kOutCodes or kCodesOnly, out null): recomputed from x, nothing reads out.
+template <int CM>
+__global__ void __launch_bounds__(256)
+rez_fine_patch_codes_kernel(const float* __restrict__ x, float* __restrict__ out, int64_t d,
+                            const float* __restrict__ l1, float fm, const RezState* __restrict__ st,
+                            const uint2* __restrict__ cand, const uint32_t* __restrict__ cand_n, uint32_t capf,
+                            int8_t* __restrict__ codes, int32_t* __restrict__ kmt, int32_t tiles) {
+    rez_fine_patch_body<CM>(x, out, d, l1, fm, st, cand, cand_n, capf, codes, kmt, tiles);
 }
 
 // KB6t: the fine clients whose threshold ties KB7 replayed.  KB6f wrote their rows with the
 // threshold's bin unselected and listed the bin; the listed coordinates that are selected (key
 // above the threshold key, or equal to it with KB7's bit) get k'' = k' -+ 1.  Grid (blocks,
 // <= list length): y strides over KB7's client list.
-__global__ void __launch_bounds__(256)
-rez_tie_patch_kernel(const float* __restrict__ x, float* __restrict__ out, int64_t d, const float* __restrict__ l1,
-                     float fm, const RezState* __restrict__ st, const uint2* __restrict__ cand,
-                     const uint32_t* __restrict__ cand_n, uint32_t capf, const uint32_t* __restrict__ tie_bits,
-                     const uint32_t* __restrict__ list) {
+template <int CM>
+__device__ __forceinline__ void rez_tie_patch_body(const float* __restrict__ x, float* __restrict__ out, int64_t d,
+                                                   const float* __restrict__ l1, float fm,
+                                                   const RezState* __restrict__ st, const uint2* __restrict__ cand,
+                                                   const uint32_t* __restrict__ cand_n, uint32_t capf,
+                                                   const uint32_t* __restrict__ tie_bits,
+                                                   const uint32_t* __restrict__ list, int8_t* __restrict__ codes,
+                                                   int32_t* __restrict__ kmt, int32_t tiles) {
     const uint32_t nl = list[0];
     for (uint32_t li = blockIdx.y; li < nl; li += gridDim.y) {
         const int64_t vec = list[1 + li];
@@ -885,9 +1049,34 @@ rez_tie_patch_kernel(const float* __restrict__ x, float* __restrict__ out, int64
             const float v = x[vec * d + c.x];
             float kp;
             (void)rez_elem(v, dp, fm, up, kp);
-            out[vec * d + c.x] = (L * torch_signf(v)) * div1(kp + adj, dpm);     // AS:687 with k''
+            if constexpr (CM != kOutOnly) {
+                int km = 0;
+                codes[vec * d + c.x] = (int8_t)rez_code(v, kp + adj, km);
+                if (km > 0) atomicMax(&kmt[vec * tiles + c.x / kSelTile], km);
+            }
+            if constexpr (CM != kCodesOnly)
+                out[vec * d + c.x] = (L * torch_signf(v)) * div1(kp + adj, dpm);     // AS:687 with k''
         }
     }
+}
+
+__global__ void __launch_bounds__(256)
+rez_tie_patch_kernel(const float* __restrict__ x, float* __restrict__ out, int64_t d, const float* __restrict__ l1,
+                     float fm, const RezState* __restrict__ st, const uint2* __restrict__ cand,
+                     const uint32_t* __restrict__ cand_n, uint32_t capf, const uint32_t* __restrict__ tie_bits,
+                     const uint32_t* __restrict__ list) {
+    rez_tie_patch_body<kOutOnly>(x, out, d, l1, fm, st, cand, cand_n, capf, tie_bits, list, nullptr, nullptr, 0);
+}
+
+// KB6t with the codes (CM: kOutCodes or kCodesOnly, out null).
+template <int CM>
+__global__ void __launch_bounds__(256)
+rez_tie_patch_codes_kernel(const float* __restrict__ x, float* __restrict__ out, int64_t d,
+                           const float* __restrict__ l1, float fm, const RezState* __restrict__ st,
+                           const uint2* __restrict__ cand, const uint32_t* __restrict__ cand_n, uint32_t capf,
+                           const uint32_t* __restrict__ tie_bits, const uint32_t* __restrict__ list,
+                           int8_t* __restrict__ codes, int32_t* __restrict__ kmt, int32_t tiles) {
+    rez_tie_patch_body<CM>(x, out, d, l1, fm, st, cand, cand_n, capf, tie_bits, list, codes, kmt, tiles);
 }
 
 // KB-small: the whole AS:644-687 for vectors shorter than GRAIN in ONE launch (the reference
@@ -899,9 +1088,12 @@ rez_tie_patch_kernel(const float* __restrict__ x, float* __restrict__ out, int64
 // (kRezAmbiguous without kRezTorchTies) and the host reruns the multi-kernel path for it.
 // Writes l1buf[vec], st[vec] (delta, flags: the info pair) and out.
 constexpr int64_t kSmallBiasedMax = kGrain - 1;
-__global__ void __launch_bounds__(256)
-biased_small_kernel(const float* __restrict__ x, float* __restrict__ out, int64_t d, float fm,
-                    const float* __restrict__ l1in, float* __restrict__ l1buf, RezState* __restrict__ st) {
+template <int CM>
+__device__ __forceinline__ void biased_small_body(const float* __restrict__ x, float* __restrict__ out, int64_t d,
+                                                  float fm, const float* __restrict__ l1in,
+                                                  float* __restrict__ l1buf, RezState* __restrict__ st,
+                                                  int8_t* __restrict__ codes, int32_t* __restrict__ kmt,
+                                                  int32_t tiles) {
     extern __shared__ uint32_t keys[];                // [d] keys of the client
     __shared__ float scr[64 * 32 + 64];
     __shared__ uint32_t h[kRadixBins];
@@ -911,6 +1103,8 @@ biased_small_kernel(const float* __restrict__ x, float* __restrict__ out, int64_
     const int64_t vec = blockIdx.x;
     const float* xv = x + vec * d;
     float* ov = out + vec * d;
+    int8_t* cvr = codes + vec * d;
+    int km = 0;
     const float L = l1in ? l1in[vec] : block_torch_sum(xv, d, scr, [](float v) { return fabsf(v); });   // AS:680
     const DivPlan dp = div_plan(L);
     const float mprime = block_torch_sum(xv, d, scr, [&](float v) {                                 // AS:648-649
@@ -990,7 +1184,9 @@ biased_small_kernel(const float* __restrict__ x, float* __restrict__ out, int64_
         float kp;
         (void)rez_elem(xv[i], dp, fm, up, kp);
         const float k2 = sel ? kp + adj : kp;          // k''
-        ov[i] = (L * torch_signf(xv[i])) * div1(k2, dpm);
+        if constexpr (CM != kOutOnly) cvr[i] = (int8_t)rez_code(xv[i], k2, km);
+        if constexpr (CM != kCodesOnly)
+            ov[i] = (L * torch_signf(xv[i])) * div1(k2, dpm);
     };
     if (!amb) {
         for (int64_t i = tid; i < d; i += 256) emit(i, on && keys[i] >= tau);
@@ -1005,10 +1201,26 @@ biased_small_kernel(const float* __restrict__ x, float* __restrict__ out, int64_
             emit(i, k > tau || (k == tau && rank++ < s.need));
         }
     }
+    if constexpr (CM != kOutOnly) rez_publish_kmax(km, kmt, vec * tiles);     // (the client's first tile slot)
     if (tid == 0) {
         l1buf[vec] = L;
         st[vec] = s;
     }
+}
+
+__global__ void __launch_bounds__(256)
+biased_small_kernel(const float* __restrict__ x, float* __restrict__ out, int64_t d, float fm,
+                    const float* __restrict__ l1in, float* __restrict__ l1buf, RezState* __restrict__ st) {
+    biased_small_body<kOutOnly>(x, out, d, fm, l1in, l1buf, st, nullptr, nullptr, 0);
+}
+
+// KB-small with the codes (CM: kOutCodes or kCodesOnly, out null).
+template <int CM>
+__global__ void __launch_bounds__(256)
+biased_small_codes_kernel(const float* __restrict__ x, float* __restrict__ out, int64_t d, float fm,
+                          const float* __restrict__ l1in, float* __restrict__ l1buf, RezState* __restrict__ st,
+                          int8_t* __restrict__ codes, int32_t* __restrict__ kmt, int32_t tiles) {
+    biased_small_body<CM>(x, out, d, fm, l1in, l1buf, st, codes, kmt, tiles);
 }
 
 }  // namespace

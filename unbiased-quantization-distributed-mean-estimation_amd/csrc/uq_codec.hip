@@ -46,7 +46,7 @@ int uq_tc_workspace_bytes(int64_t n, int64_t d, size_t* bytes_out) {
 int uq_tc_encode(const int8_t* codes, const float* l1, int64_t n, int64_t d, int64_t m, int32_t flags, uint8_t* msgs,
                  size_t msgs_bytes, uint64_t* offsets, void* ws, size_t ws_bytes, void* stream) {
     if (n < 0 || d < 0 || d > ((int64_t)1 << 31) || m < 0) return fail(UQ_E_INVALID, "bad n / d / m");
-    if (flags & ~1) return fail(UQ_E_INVALID, "unknown codec flags");
+    if (flags & ~(UQ_TC_EXACT_ZERO_SIGNS | UQ_TC_BIASED_FORM)) return fail(UQ_E_INVALID, "unknown codec flags");
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) return offsets ? hip_check(hipMemsetAsync(offsets, 0, 8, st), "offsets") : fail(UQ_E_INVALID, "null offsets");
     if (!l1 || !msgs || !offsets || !ws || (d > 0 && !codes)) return fail(UQ_E_INVALID, "null pointer");
@@ -89,7 +89,7 @@ int uq_tc_encode(const int8_t* codes, const float* l1, int64_t n, int64_t d, int
         // d == 0: header-only messages, written by one "chunk" each
         for (int64_t j0 = 0; j0 < n; j0 += kMaxGridY) {
             const int64_t nj = std::min<int64_t>(kMaxGridY, n - j0);
-            hipLaunchKernelGGL(tc_pack_kernel, dim3(1, (unsigned)nj), dim3(256), 0, st, d, m, exact, l1 + j0, tabs + j0,
+            hipLaunchKernelGGL(tc_pack_kernel, dim3(1, (unsigned)nj), dim3(256), 0, st, d, m, flags, l1 + j0, tabs + j0,
                                scratch, cwords, states, offsets + j0, msgs);
             if ((rc = hip_check(hipGetLastError(), "tc_pack_kernel launch"))) return rc;
         }
@@ -97,7 +97,7 @@ int uq_tc_encode(const int8_t* codes, const float* l1, int64_t n, int64_t d, int
     }
     for (int64_t j0 = 0; j0 < n; j0 += kMaxGridY) {
         const int64_t nj = std::min<int64_t>(kMaxGridY, n - j0);
-        hipLaunchKernelGGL(tc_pack_kernel, dim3((unsigned)nch, (unsigned)nj), dim3(256), 0, st, d, m, exact, l1 + j0,
+        hipLaunchKernelGGL(tc_pack_kernel, dim3((unsigned)nch, (unsigned)nj), dim3(256), 0, st, d, m, flags, l1 + j0,
                            tabs + j0, scratch + j0 * nch * ((int64_t)tc_lanes(d) * kTcSteps), cwords + j0 * nch,
                            states + j0 * nch * tc_lanes(d), offsets + j0, msgs);
         if ((rc = hip_check(hipGetLastError(), "tc_pack_kernel launch"))) return rc;

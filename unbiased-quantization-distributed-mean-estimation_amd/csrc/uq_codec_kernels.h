@@ -459,7 +459,7 @@ __device__ __forceinline__ void tc_put32(uint8_t* p, uint32_t v) {   // 4-byte a
 // its words; chunk 0's also the fixed header and the frequency table; the last chunk's the
 // padding word.
 __global__ void __launch_bounds__(256)
-tc_pack_kernel(int64_t d, int64_t m, int exact, const float* __restrict__ l1, const TcTable* __restrict__ tabs,
+tc_pack_kernel(int64_t d, int64_t m, int flags, const float* __restrict__ l1, const TcTable* __restrict__ tabs,
                const uint16_t* __restrict__ scratch, const uint32_t* __restrict__ cwords,
                const uint32_t* __restrict__ states, const uint64_t* __restrict__ offsets, uint8_t* __restrict__ msgs) {
     const int tid = threadIdx.x;
@@ -488,7 +488,7 @@ tc_pack_kernel(int64_t d, int64_t m, int exact, const float* __restrict__ l1, co
         if (tid == 0) {
             const uint64_t size = offsets[vec + 1] - offsets[vec];
             tc_put32(msg + 0, kTcMagic);
-            tc_put32(msg + 4, 1u | ((uint32_t)(exact ? 1 : 0) << 16));
+            tc_put32(msg + 4, 1u | ((uint32_t)(flags & 3) << 16));     // version 1 | UQ_TC_* flags
             tc_put32(msg + 8, (uint32_t)(uint64_t)d);
             tc_put32(msg + 12, (uint32_t)((uint64_t)d >> 32));
             tc_put32(msg + 16, (uint32_t)(uint64_t)m);

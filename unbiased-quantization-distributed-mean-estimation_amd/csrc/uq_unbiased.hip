@@ -499,7 +499,14 @@ int uq_type_unbiased_f32(const float* x, float* out, int64_t n, int64_t d, int64
 
 int uq_codes_decode_f32(const int8_t* codes, const float* l1, int64_t n, int64_t d, int64_t m, float* out,
                         void* stream) {
+    return uq_codes_decode_form_f32(codes, l1, n, d, m, UQ_FORM_UNBIASED, out, stream);
+}
+
+int uq_codes_decode_form_f32(const int8_t* codes, const float* l1, int64_t n, int64_t d, int64_t m, int32_t form,
+                             float* out, void* stream) {
     if (n < 0 || d < 0 || m < 0) return fail(UQ_E_INVALID, "n, d and m must be >= 0");
+    if (form != UQ_FORM_UNBIASED && form != UQ_FORM_BIASED) return fail(UQ_E_INVALID, "unknown codes form");
+    if (form == UQ_FORM_BIASED && m < 1) return fail(UQ_E_INVALID, "m must be >= 1 for biased codes");
     if (n == 0 || d == 0) return UQ_OK;
     if (!codes || !l1 || !out) return fail(UQ_E_INVALID, "null pointer");
     hipStream_t st = (hipStream_t)stream;
@@ -507,7 +514,12 @@ int uq_codes_decode_f32(const int8_t* codes, const float* l1, int64_t n, int64_t
     if (chunks > 0x7FFFFFFF) return fail(UQ_E_INVALID, "d too large");
     const bool vec = aligned16(codes) && aligned16(out) && d % 16 == 0;
     dim3 grid((unsigned)chunks, (unsigned)n);
-    if (vec)
+    if (form == UQ_FORM_BIASED) {
+        if (vec)
+            hipLaunchKernelGGL(codes_decode_biased_kernel<true>, grid, dim3(256), 0, st, codes, l1, d, (float)m, out);
+        else
+            hipLaunchKernelGGL(codes_decode_biased_kernel<false>, grid, dim3(256), 0, st, codes, l1, d, (float)m, out);
+    } else if (vec)
         hipLaunchKernelGGL(codes_decode_kernel<true>, grid, dim3(256), 0, st, codes, l1, d, (float)m, out);
     else
         hipLaunchKernelGGL(codes_decode_kernel<false>, grid, dim3(256), 0, st, codes, l1, d, (float)m, out);
@@ -517,7 +529,15 @@ int uq_codes_decode_f32(const int8_t* codes, const float* l1, int64_t n, int64_t
 int uq_codes_q_mean_ld_f32(const int8_t* codes, int64_t ldc, const float* q, int64_t ldq, const float* l1,
                            const int32_t* kmax, int64_t n, int64_t d, int64_t m, float n_div, int32_t accumulate,
                            float* est, void* stream) {
+    return uq_codes_mean_form_f32(codes, ldc, q, ldq, l1, kmax, n, d, m, UQ_FORM_UNBIASED, n_div, accumulate, est, stream);
+}
+
+int uq_codes_mean_form_f32(const int8_t* codes, int64_t ldc, const float* q, int64_t ldq, const float* l1,
+                           const int32_t* kmax, int64_t n, int64_t d, int64_t m, int32_t form, float n_div,
+                           int32_t accumulate, float* est, void* stream) {
     if (n < 0 || d < 0 || m < 0) return fail(UQ_E_INVALID, "n, d and m must be >= 0");
+    if (form != UQ_FORM_UNBIASED && form != UQ_FORM_BIASED) return fail(UQ_E_INVALID, "unknown codes form");
+    if (form == UQ_FORM_BIASED && m < 1) return fail(UQ_E_INVALID, "m must be >= 1 for biased codes");
     if (d == 0) return UQ_OK;
     if (!est || (n > 0 && (!codes || !l1 || !kmax))) return fail(UQ_E_INVALID, "null pointer");
     if (q && ldq < d) return fail(UQ_E_INVALID, "ldq must be >= d");
@@ -527,6 +547,18 @@ int uq_codes_q_mean_ld_f32(const int8_t* codes, int64_t ldc, const float* q, int
     const int64_t blocks = (d + kCodesMeanThreads * kMeanCpt - 1) / (kCodesMeanThreads * kMeanCpt);
     if (blocks > 0x7FFFFFFF) return fail(UQ_E_INVALID, "d too large");
     const dim3 tb(kCodesMeanThreads);
+    if (form == UQ_FORM_BIASED) {
+        if (vec && d % (kCodesMeanThreads * kMeanCpt) == 0)
+            hipLaunchKernelGGL((codes_mean_biased_kernel<true, true>), dim3((unsigned)blocks), tb, 0, st, codes, ldc, l1, kmax,
+                               n, d, (float)m, n_div, accumulate, est, q, ldq);
+        else if (vec)
+            hipLaunchKernelGGL(codes_mean_biased_kernel<true>, dim3((unsigned)blocks), tb, 0, st, codes, ldc, l1, kmax, n, d,
+                               (float)m, n_div, accumulate, est, q, ldq);
+        else
+            hipLaunchKernelGGL(codes_mean_biased_kernel<false>, dim3((unsigned)blocks), tb, 0, st, codes, ldc, l1, kmax, n, d,
+                               (float)m, n_div, accumulate, est, q, ldq);
+        return hip_check(hipGetLastError(), "codes_mean_biased_kernel launch");
+    }
     if (vec && d % (kCodesMeanThreads * kMeanCpt) == 0)
         hipLaunchKernelGGL((codes_mean_kernel<true, true>), dim3((unsigned)blocks), tb, 0, st, codes, ldc, l1, kmax, n,
                            d, (float)m, n_div, accumulate, est, q, ldq);

@@ -1456,15 +1456,23 @@ __device__ __forceinline__ float decode_one(int8_t c, const float* tab) {
     return __uint_as_float(__float_as_uint(tab[k]) ^ ((uint32_t)ci & 0x80000000u));
 }
 
-template <bool VEC>
-__global__ void __launch_bounds__(256)
-codes_decode_kernel(const int8_t* __restrict__ codes, const float* __restrict__ l1, int64_t d, float fm,
-                    float* __restrict__ out) {
+// The decode table entry of count k in either form of the type codes (uq_dme.h UQ_FORM_*):
+// unbiased |q| = RN(RN(L1*k)/f32(m)) (AS:640); biased |q| = RN(L1*RN(k/f32(m))) (AS:687), the
+// quotient by the biased kernels' correctly rounded division (div1 over div_plan_m).
+template <bool BIASED>
+__device__ __forceinline__ float code_table_entry(float L, int k, float fm) {
+    if constexpr (BIASED) return L * div1((float)k, div_plan_m(fm));
+    else return (L * (float)k) / fm;
+}
+
+template <bool VEC, bool BIASED>
+__device__ __forceinline__ void codes_decode_body(const int8_t* __restrict__ codes, const float* __restrict__ l1,
+                                                  int64_t d, float fm, float* __restrict__ out) {
     __shared__ float tab[128];
     const int64_t vec = blockIdx.y;
     const int tid = threadIdx.x;
     const float L = l1[vec];
-    if (tid < 128) tab[tid] = (L * (float)tid) / fm;
+    if (tid < 128) tab[tid] = code_table_entry<BIASED>(L, tid, fm);
     __syncthreads();
     const int64_t i0 = (int64_t)blockIdx.x * kDecChunk + (int64_t)tid * 16;
     const int8_t* cr = codes + vec * d;
@@ -1482,6 +1490,21 @@ codes_decode_kernel(const int8_t* __restrict__ codes, const float* __restrict__ 
     } else {
         for (int64_t i = i0; i < i0 + 16 && i < d; ++i) orow[i] = decode_one(cr[i], tab);
     }
+}
+
+template <bool VEC>
+__global__ void __launch_bounds__(256)
+codes_decode_kernel(const int8_t* __restrict__ codes, const float* __restrict__ l1, int64_t d, float fm,
+                    float* __restrict__ out) {
+    codes_decode_body<VEC, false>(codes, l1, d, fm, out);
+}
+
+// The biased form's decode (uq_codes_decode_form_f32 with UQ_FORM_BIASED).
+template <bool VEC>
+__global__ void __launch_bounds__(256)
+codes_decode_biased_kernel(const int8_t* __restrict__ codes, const float* __restrict__ l1, int64_t d, float fm,
+                           float* __restrict__ out) {
+    codes_decode_body<VEC, true>(codes, l1, d, fm, out);
 }
 
 // est[i] (+)= q_j[i] / n_div for clients j in order, q decoded from codes.  Each thread
@@ -1518,6 +1541,7 @@ __device__ __forceinline__ void mean_add_batch(float (&e)[kMeanCpt], const uint2
 }
 
 // Tables of clients j0 .. j0+nb-1 into tabn (callers bracket it with barriers).
+template <bool BIASED = false>
 __device__ __forceinline__ void mean_build_tables(float (*tabn)[256], const float* __restrict__ l1,
                                                   const int32_t* __restrict__ kmaxv, int64_t j0, int nb, int wid,
                                                   int lane, float fm, float n_div) {
@@ -1525,7 +1549,7 @@ __device__ __forceinline__ void mean_build_tables(float (*tabn)[256], const floa
         const float L = l1[j0 + jj];                // wave-uniform: scalar loads
         const int km = min(127, max(0, kmaxv[j0 + jj]));
         for (int k = lane; k <= km; k += kWave) {
-            const float v = ((L * (float)k) / fm) / n_div;
+            const float v = code_table_entry<BIASED>(L, k, fm) / n_div;
             tabn[jj][k] = v;                        // code k
             tabn[jj][255 - k] = -v;                 // code ~k = -k-1 -> byte 255-k; (-a)/n = -(a/n)
         }
@@ -1570,11 +1594,11 @@ __device__ __forceinline__ void mean_add_mixed(float (&e)[kMeanCpt], const int8_
 // kMeanCpt), so no
 // per-thread `full` test anywhere (a per-thread guard around the adds cost the loads'
 // overlap in other kernels here).
-template <bool VEC, bool ALL = false>
-__global__ void __launch_bounds__(kCodesMeanThreads)
-codes_mean_kernel(const int8_t* __restrict__ codes, int64_t ldc, const float* __restrict__ l1,
-                  const int32_t* __restrict__ kmaxv, int64_t n, int64_t d, float fm, float n_div, int accumulate,
-                  float* __restrict__ est, const float* __restrict__ q, int64_t ldq) {
+template <bool VEC, bool ALL, bool BIASED>
+__device__ __forceinline__ void codes_mean_body(const int8_t* __restrict__ codes, int64_t ldc,
+                                                const float* __restrict__ l1, const int32_t* __restrict__ kmaxv,
+                                                int64_t n, int64_t d, float fm, float n_div, int accumulate,
+                                                float* __restrict__ est, const float* __restrict__ q, int64_t ldq) {
     __shared__ float tabn[kMeanClients][256];     // indexed by the raw code byte, sign included
     __shared__ uint32_t s_ovf;
     const int tid = threadIdx.x;
@@ -1604,7 +1628,7 @@ codes_mean_kernel(const int8_t* __restrict__ codes, int64_t ldc, const float* __
             const int nb = (int)min((int64_t)kMeanClients, n - j0);
             const uint32_t ovf = mean_ovf_mask(kmaxv, j0, nb);
             __syncthreads();
-            mean_build_tables(tabn, l1, kmaxv, j0, nb, wid, lane, fm, n_div);
+            mean_build_tables<BIASED>(tabn, l1, kmaxv, j0, nb, wid, lane, fm, n_div);
             __syncthreads();
             mean_add_mixed(e, codes, ldc, q, ldq, tabn, ovf, j0, nb, i0, d, n_div);
         }
@@ -1618,7 +1642,7 @@ codes_mean_kernel(const int8_t* __restrict__ codes, int64_t ldc, const float* __
     for (int64_t g = 0; g < groups; ++g) {
         const int64_t j0 = g * kMeanClients;
         __syncthreads();                            // previous group's tables no longer read
-        mean_build_tables(tabn, l1, kmaxv, j0, kMeanClients, wid, lane, fm, n_div);
+        mean_build_tables<BIASED>(tabn, l1, kmaxv, j0, kMeanClients, wid, lane, fm, n_div);
         __syncthreads();
         if (VEC) {
             mean_load_batch(wb, cbase + (j0 + kMeanUnroll) * ldc, ldc);
@@ -1633,7 +1657,7 @@ codes_mean_kernel(const int8_t* __restrict__ codes, int64_t ldc, const float* __
     const int nr = (int)(n - jr);
     if (nr > 0) {                                   // the last n % kMeanClients clients
         __syncthreads();
-        mean_build_tables(tabn, l1, kmaxv, jr, nr, wid, lane, fm, n_div);
+        mean_build_tables<BIASED>(tabn, l1, kmaxv, jr, nr, wid, lane, fm, n_div);
         __syncthreads();
         if (full) {
             for (int jj = 0; jj < nr; ++jj) {
@@ -1655,6 +1679,24 @@ codes_mean_kernel(const int8_t* __restrict__ codes, int64_t ldc, const float* __
         for (int k = 0; k < kMeanCpt; ++k)
             if (i0 + k < d) est[i0 + k] = e[k];
     }
+}
+
+template <bool VEC, bool ALL = false>
+__global__ void __launch_bounds__(kCodesMeanThreads)
+codes_mean_kernel(const int8_t* __restrict__ codes, int64_t ldc, const float* __restrict__ l1,
+                  const int32_t* __restrict__ kmaxv, int64_t n, int64_t d, float fm, float n_div, int accumulate,
+                  float* __restrict__ est, const float* __restrict__ q, int64_t ldq) {
+    codes_mean_body<VEC, ALL, false>(codes, ldc, l1, kmaxv, n, d, fm, n_div, accumulate, est, q, ldq);
+}
+
+// The biased form's mean (uq_codes_mean_form_f32 with UQ_FORM_BIASED): the same loops over
+// tables of L1*RN(k/m).
+template <bool VEC, bool ALL = false>
+__global__ void __launch_bounds__(kCodesMeanThreads)
+codes_mean_biased_kernel(const int8_t* __restrict__ codes, int64_t ldc, const float* __restrict__ l1,
+                         const int32_t* __restrict__ kmaxv, int64_t n, int64_t d, float fm, float n_div,
+                         int accumulate, float* __restrict__ est, const float* __restrict__ q, int64_t ldq) {
+    codes_mean_body<VEC, ALL, true>(codes, ldc, l1, kmaxv, n, d, fm, n_div, accumulate, est, q, ldq);
 }
 
 // ---- 4-bit type codes (the bench pipeline "codes4") ------------------------------------

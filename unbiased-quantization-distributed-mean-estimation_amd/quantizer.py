@@ -23,7 +23,7 @@ import torch
 from . import _lib, _runtime
 from ._runtime import (as_batch_f32, as_vector_f32, check_status, get_torch_threads, ptr,  # noqa: F401 (re-exports)
                        set_torch_threads, stream_ptr, workspace_for)
-from .codes import TypeCodes
+from .codes import TypeCodes, form_index
 from .outpool import POOL
 from .rates import RATE_TABLE, rate_to_m
 
@@ -135,20 +135,23 @@ def quantize_encode(x, bits_per_dimension=1, X=None, *, m: int | None = None, to
 
 
 def decode(tc) -> torch.Tensor:
-    """Rebuild the dequantized batch from type codes (bit-identical to quantize_dequantize)."""
+    """Rebuild the dequantized batch from type codes in their form: bit-identical to
+    quantize_dequantize (tc.form "unbiased") or biased_quantize ("biased")."""
     dev = _runtime.device()
     codes = tc.codes.to(dev).contiguous()
     l1 = tc.l1.to(device=dev, dtype=torch.float32).contiguous()
     n, d = codes.shape
     out = torch.empty((n, d), dtype=torch.float32, device=dev)
-    _lib.check(_lib.load().uq_codes_decode_f32(ptr(codes), ptr(l1), n, d, int(tc.m), ptr(out), stream_ptr(dev)),
-               "uq_codes_decode_f32")
+    _lib.check(_lib.load().uq_codes_decode_form_f32(ptr(codes), ptr(l1), n, d, int(tc.m), form_index(tc.form), ptr(out),
+                                                    stream_ptr(dev)), "uq_codes_decode_form_f32")
     return out
 
 
-def codes_mean(tc, n_div, est=None, accumulate: bool = False) -> torch.Tensor:
+def codes_mean(tc, n_div, est=None, accumulate: bool = False, q=None) -> torch.Tensor:
     """ND:137-138 from type codes: est (+)= decode(codes)[j] / n_div over clients j in order,
-    bit-identical to client_mean(decode(tc), n_div)."""
+    bit-identical to client_mean(decode(tc), n_div), in the codes' form (tc.form).  q: the
+    dequantized batch [n, d] beside the codes; a client whose codes must not be decoded
+    (tc.overflow == 128) is then read from it."""
     dev = _runtime.device()
     codes = tc.codes.to(dev).contiguous()
     l1 = tc.l1.to(device=dev, dtype=torch.float32).contiguous()
@@ -157,8 +160,13 @@ def codes_mean(tc, n_div, est=None, accumulate: bool = False) -> torch.Tensor:
         est = torch.empty(d, dtype=torch.float32, device=dev)
         accumulate = False
     kmax = tc.overflow.to(device=dev, dtype=torch.int32).contiguous()
-    _lib.check(_lib.load().uq_codes_mean_f32(ptr(codes), ptr(l1), ptr(kmax), n, d, int(tc.m), float(n_div),
-                                             int(bool(accumulate)), ptr(est), stream_ptr(dev)), "uq_codes_mean_f32")
+    if q is not None:
+        q = q.to(device=dev, dtype=torch.float32).contiguous()
+        if q.shape != codes.shape:
+            raise ValueError("q must have the codes' shape")
+    _lib.check(_lib.load().uq_codes_mean_form_f32(ptr(codes), d, ptr(q), d, ptr(l1), ptr(kmax), n, d, int(tc.m),
+                                                  form_index(tc.form), float(n_div), int(bool(accumulate)), ptr(est),
+                                                  stream_ptr(dev)), "uq_codes_mean_form_f32")
     return est
 
 
