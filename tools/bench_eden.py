@@ -1,14 +1,113 @@
 """Time EDEN + RHT (uq_eden_f32) on a resident synthetic batch.
 
-    python tools/bench_eden.py --clients 1024 --dim 1048576 --bits 1"""
+    python tools/bench_eden.py --clients 1024 --dim 1048576 --bits 1
+
+    python tools/bench_eden.py --parent-lib OLD.so [--reps 20] [--json OUT.json]
+
+--parent-lib: another build of the library (build_ext.build(src_dir=..., out=...) of an earlier
+revision).  Its sender (uq_eden_compress_f32 / uq_eden_compress_frac_f32; the norm alone through
+uq_eden_norm_f32 mode 2) takes turns with this tree's, call for call in one process, each on a
+workspace and outputs of its own, device events around each call, the order swapped every
+repetition, over the shapes that take the segmented chains (AB_SHAPES).  Compress only: the
+receiver's transform would dilute a difference in the sender.  Per shape: median and 10th / 90th
+percentile of both, whether both wrote the same bits, and `within_noise`: this tree's median is at
+most the parent's plus the parent's own 10th-90th percentile spread in that run."""
 import argparse
+import ctypes
 import json
 import os
 import sys
 
+import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+# (clients, dim, bits; bits None: the norm alone).  DESIGN.md §4.3's dispatch table: the per-call
+# drop-ins, config C4, the largest segmented dot, the largest segmented norm batch, two fractional rates
+AB_SHAPES = [(n, d, b) for n, d in ((1, 1 << 20), (1, 1 << 22), (101, 1 << 22), (128, 1 << 20)) for b in (1, 2)]
+AB_SHAPES += [(256, 1 << 14, None), (1, 1 << 20, 1.5), (101, 1 << 22, 1.5)]
+
+
+def sender_call(lib, x, bits, tab, rows, sb, mb):
+    """(run, outputs): the sender of the ctypes library `lib` on x [n, d], on a workspace of its own."""
+    from uqdme_amd import _runtime
+    p, sp = _runtime.ptr, _runtime.stream_ptr(x.device)
+    n, d = x.shape
+    nb = ctypes.c_size_t()
+    size_fn = lib.uq_eden_norm_workspace_bytes if bits is None else lib.uq_eden_workspace_bytes
+    assert size_fn(n, d, ctypes.byref(nb)) == 0
+    ws = torch.zeros(max(1, nb.value), dtype=torch.uint8, device=x.device)
+    scale = torch.empty(n, dtype=torch.float32, device=x.device)        # (the norm alone: the norms)
+    bins = torch.empty((n, d), dtype=torch.uint8, device=x.device)
+    if bits is None:
+        run = lambda: lib.uq_eden_norm_f32(p(x), n, d, 2, p(scale), p(ws), ws.numel(), sp)
+    elif mb is not None:
+        run = lambda: lib.uq_eden_compress_frac_f32(p(x), n, d, p(tab), p(rows), p(sb), p(mb), p(rows), p(bins), p(scale),
+                                                    p(ws), ws.numel(), sp)
+    else:
+        run = lambda: lib.uq_eden_compress_f32(p(x), n, d, bits, p(tab), p(rows), p(bins), p(scale), p(ws), ws.numel(), sp)
+
+    def checked():
+        rc = run()
+        assert rc == 0, rc
+    return checked, (bins, scale)
+
+
+def bench_ab(a):
+    import uqdme  # noqa: F401  (loads the package as uqdme_amd)
+    from uqdme_amd import _lib, eden
+    libs = {"new": _lib.load(), "parent": ctypes.CDLL(a.parent_lib)}
+    for name, (res, args) in _lib.SIGNATURES.items():
+        if name.startswith("uq_eden_"):
+            fn = getattr(libs["parent"], name)
+            fn.restype, fn.argtypes = res, args
+    dev = torch.device("cuda")
+    g = torch.Generator(device=dev).manual_seed(3)
+    results = []
+    for n, d, bits in AB_SHAPES:
+        x = torch.randn(n, d, generator=g, device=dev)
+        seeds = torch.arange(min(n, 100))
+        rows = (torch.arange(n) % 100).to(torch.int32).to(dev)
+        tab = sb = mb = None
+        if bits is not None:
+            tab = eden.rht_signs(seeds, d, dev)
+            sb = eden.rht_sign_bits(tab)
+            if bits not in (1, 2):
+                mb = eden.eden_mask_bits(seeds, d, eden._threshold(bits - 1.0), dev)
+        calls = {k: sender_call(lib, x, bits, tab, rows, sb, mb) for k, lib in libs.items()}
+        for run, _ in calls.values():
+            for _ in range(3):
+                run()
+        torch.cuda.synchronize()
+        times = {k: [] for k in calls}
+        for rep in range(a.reps):
+            for k in ("new", "parent")[::1 if rep % 2 == 0 else -1]:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                calls[k][0]()
+                e1.record()
+                e1.synchronize()
+                times[k].append(e0.elapsed_time(e1))
+        outs = [calls[k][1] for k in ("new", "parent")]
+        same = bool(torch.equal(outs[0][1].view(torch.int32), outs[1][1].view(torch.int32)) and
+                    (bits is None or torch.equal(outs[0][0], outs[1][0])))
+        ms = {k: {"median": round(float(np.median(v)), 4), "p10": round(float(np.percentile(v, 10)), 4),
+                  "p90": round(float(np.percentile(v, 90)), 4)} for k, v in times.items()}
+        par = ms["parent"]
+        row = {"clients": n, "d": d, "bits": bits, "call": "uq_eden_norm_f32 mode 2" if bits is None else "compress",
+               "ms": ms, "same_bits": same,
+               "within_noise": ms["new"]["median"] <= par["median"] + (par["p90"] - par["p10"])}
+        print(json.dumps(row), flush=True)
+        results.append(row)
+        del x, tab, sb, mb, calls, outs
+        torch.cuda.empty_cache()
+    res = {"tool": "bench_eden --parent-lib", "reps": a.reps, "shapes": results,
+           "all_same_bits": all(r["same_bits"] for r in results), "all_within_noise": all(r["within_noise"] for r in results)}
+    print(json.dumps({k: v for k, v in res.items() if k != "shapes"}))
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(res, f, indent=1)
 
 
 def main():
@@ -17,7 +116,12 @@ def main():
     ap.add_argument("--dim", type=int, default=1 << 20)
     ap.add_argument("--bits", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--parent-lib", default=None, help="an earlier build whose sender is timed beside this tree's")
+    ap.add_argument("--reps", type=int, default=20, help="--parent-lib: alternations per shape")
+    ap.add_argument("--json", default=None, help="--parent-lib: also write the result here")
     a = ap.parse_args()
+    if a.parent_lib:
+        return bench_ab(a)
     import uqdme
     g = torch.Generator(device="cuda").manual_seed(3)
     x = torch.randn(a.clients, a.dim, generator=g, device="cuda")

@@ -172,12 +172,19 @@ int launch_norm(const EdenPlan& P, const float* v, int64_t n, char* region, floa
     const int cap = P.tab_cap;
     const dim3 grid((unsigned)(K / kSegPerWG), (unsigned)n);
     hipLaunchKernelGGL(eden_segsum_kernel, grid, dim3(256), 0, st, v, D, s.segsum);
-    hipLaunchKernelGGL(eden_segscan_kernel, dim3(8u, (unsigned)n), dim3(256), 0, st, s.segsum, K, s.g, s.cnt);
+    hipLaunchKernelGGL(eden_segscan_kernel<8>, dim3(8u, (unsigned)n), dim3(256), 0, st, s.segsum, K, s.g, s.cnt);
     hipLaunchKernelGGL(eden_segchain_kernel, grid, dim3(256), 0, st, v, D, s.g, s.e, s.kind, s.cnt, s.tseg, cap);
     hipLaunchKernelGGL(eden_segtab_kernel, dim3((unsigned)cap, (unsigned)n), dim3(256), 0, st, v, D, s.g, s.cnt, s.tseg,
                        s.tab, cap);
     hipLaunchKernelGGL(eden_segwalk_kernel, dim3((unsigned)n), dim3(512), 0, st, v, D, s.g, s.e, s.kind, s.tab, nrm, cap);
     return launched("eden segmented norm launch");
+}
+
+// f(FRAC) for a plan's rate: the mask-aware instances of the segmented dot's kernels, or the 1- and 2-bit ones
+template <class F>
+void select_frac(bool frac, F&& f) {
+    if (frac) f(Flag<true>{});
+    else f(Flag<false>{});
 }
 
 // KE4s (few clients): the bins and the dot's 64 chains in segments, in the segmented norm's
@@ -188,28 +195,17 @@ int launch_eden_dotseg(const EdenPlan& P, const float* v, int64_t n, float sqrtD
     const int64_t D = P.D, K = D / kEdenTile;
     const int cap = P.tab_cap;
     hipLaunchKernelGGL(eden_thresh_kernel, dim3((unsigned)n), dim3(64), 0, st, nrm, tab, s.thr4);
-    if (P.frac) {       // the same chain of kernels, each element's table by the mask rows
-        hipLaunchKernelGGL(eden_dseg_sum_frac_kernel, dim3((unsigned)K, (unsigned)n), dim3(256), 0, st, v, D, sqrtD, nrm,
-                           s.thr4, tab, bins, s.segsum, m);
-        hipLaunchKernelGGL(eden_segscan_l_kernel<64>, dim3(64u, (unsigned)n), dim3(256), 0, st, s.segsum, K, s.g, s.cnt);
-        hipLaunchKernelGGL(eden_dseg_chain_frac_kernel, dim3((unsigned)(K / kDSegTiles), (unsigned)n), dim3(256), 0, st, v, D,
+    select_frac(P.frac, [&](auto F) {
+        hipLaunchKernelGGL(eden_dseg_sum_kernel<F()>, dim3((unsigned)K, (unsigned)n), dim3(256), 0, st, v, D, sqrtD, nrm, s.thr4,
+                           tab, bins, s.segsum, m);
+        hipLaunchKernelGGL(eden_segscan_kernel<64>, dim3(64u, (unsigned)n), dim3(256), 0, st, s.segsum, K, s.g, s.cnt);
+        hipLaunchKernelGGL(eden_dseg_chain_kernel<F()>, dim3((unsigned)(K / kDSegTiles), (unsigned)n), dim3(256), 0, st, v, D,
                            sqrtD, nrm, s.thr4, tab, s.g, s.e, s.kind, s.cnt, s.tseg, cap, m);
-        hipLaunchKernelGGL(eden_dseg_tab_frac_kernel, dim3((unsigned)cap, (unsigned)n), dim3(256), 0, st, v, D, sqrtD, nrm,
+        hipLaunchKernelGGL(eden_dseg_tab_kernel<F()>, dim3((unsigned)cap, (unsigned)n), dim3(256), 0, st, v, D, sqrtD, nrm,
                            s.thr4, tab, s.g, s.cnt, s.tseg, s.tab, cap, m);
-        hipLaunchKernelGGL(eden_dseg_walk_frac_kernel, dim3(8u, (unsigned)n), dim3(512), 0, st, v, D, sqrtD, nrm, s.thr4, tab,
+        hipLaunchKernelGGL(eden_dseg_walk_kernel<F()>, dim3(8u, (unsigned)n), dim3(512), 0, st, v, D, sqrtD, nrm, s.thr4, tab,
                            s.g, s.e, s.kind, s.tab, s.acc64, cap, m);
-        hipLaunchKernelGGL(eden_dseg_final_kernel, dim3((unsigned)n), dim3(64), 0, st, s.acc64, nrm, scale);
-        return launched("eden segmented dot launch");
-    }
-    hipLaunchKernelGGL(eden_dseg_sum_kernel, dim3((unsigned)K, (unsigned)n), dim3(256), 0, st, v, D, sqrtD, nrm, s.thr4, tab,
-                       bins, s.segsum);
-    hipLaunchKernelGGL(eden_segscan_l_kernel<64>, dim3(64u, (unsigned)n), dim3(256), 0, st, s.segsum, K, s.g, s.cnt);
-    hipLaunchKernelGGL(eden_dseg_chain_kernel, dim3((unsigned)(K / kDSegTiles), (unsigned)n), dim3(256), 0, st, v, D, sqrtD,
-                       nrm, s.thr4, tab, s.g, s.e, s.kind, s.cnt, s.tseg, cap);
-    hipLaunchKernelGGL(eden_dseg_tab_kernel, dim3((unsigned)cap, (unsigned)n), dim3(256), 0, st, v, D, sqrtD, nrm, s.thr4,
-                       tab, s.g, s.cnt, s.tseg, s.tab, cap);
-    hipLaunchKernelGGL(eden_dseg_walk_kernel, dim3(8u, (unsigned)n), dim3(512), 0, st, v, D, sqrtD, nrm, s.thr4, tab, s.g,
-                       s.e, s.kind, s.tab, s.acc64, cap);
+    });
     hipLaunchKernelGGL(eden_dseg_final_kernel, dim3((unsigned)n), dim3(64), 0, st, s.acc64, nrm, scale);
     return launched("eden segmented dot launch");
 }

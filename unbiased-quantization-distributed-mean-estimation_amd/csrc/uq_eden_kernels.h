@@ -1158,109 +1158,68 @@ eden_segsum_kernel(const float* __restrict__ v, int64_t D, double* __restrict__ 
     segsum[(client * 8 + l) * K + seg0 + sl] = (acc[0] + acc[1]) + (acc[2] + acc[3]);
 }
 
-// one workgroup per (lane, client): the exclusive prefix of the lane's K segment sums, in
-// rounds of 1024 (4 per thread, coalesced); lane 0's workgroup zeroes the table count
-__global__ void __launch_bounds__(256)
-eden_segscan_kernel(const double* __restrict__ segsum, int64_t K, float* __restrict__ g, int32_t* __restrict__ tabcnt) {
-    __shared__ double wsum[256 / kWave];
-    const int tid = threadIdx.x, lane = tid & (kWave - 1), wid = tid / kWave;
-    const int l = blockIdx.x;
-    const int64_t client = blockIdx.y;
-    if (tid == 0 && l == 0) tabcnt[client] = 0;
-    const double* src = segsum + (client * 8 + l) * K;
-    float* dst = g + (client * 8 + l) * K;
-    double carry = 0.0;
-    for (int64_t r0 = 0; r0 < K; r0 += 1024) {
-        double x[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int64_t i = r0 + 4 * tid + k;
-            x[k] = i < K ? src[i] : 0.0;
-        }
-        const double t = (x[0] + x[1]) + (x[2] + x[3]);
-        const double incl = wave_incl_scan(t, lane);
-        if (lane == kWave - 1) wsum[wid] = incl;
-        __syncthreads();
-        double run = carry + wave_prev(incl), tot = carry;
-#pragma unroll
-        for (int w = 0; w < 256 / kWave; ++w) {
-            if (w < wid) run += wsum[w];
-            tot += wsum[w];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int64_t i = r0 + 4 * tid + k;
-            if (i < K) dst[i] = (float)run;
-            run += x[k];
-        }
-        carry = tot;
-    }
+// ---- the segmented chains' argument, once: the norm (KE2s) and the dot (KE4s) share it -----
+// A term policy says what differs between the two: kChains chains per client, index(s, i, l) =
+// where the row holds segment s, step i of chain l, and factor(x, index) = the step's other
+// factor, so that a step is acc = fmaf(factor, x, acc).  g / e / kind are [client][chain][segment],
+// a listed segment's code in tabseg is s * kChains + l.
+struct NormTerm {                                        // torch.norm: lane l of 8 runs x * x
+    static constexpr int kChains = 8;
+    static __device__ __forceinline__ int64_t index(int64_t s, int i, int l) { return 8 * (s * kSegSteps + i) + l; }
+    __device__ __forceinline__ float factor(float x, int64_t) const { return x; }
+};
+
+// One step r = fmaf(a, x, b) of a guess chain: `tie`, or true when r is (or may be) a rounded midpoint.
+// (b + a*x) - r exactly (fp64: b - r is exact when their exponents are within 28, and the fma
+// returns the residual exactly whenever it is one of the values tested): a midpoint is half a
+// grid step, u/2, or u/4 just below a power of two.  (The running flag goes through here: with
+// `tie || seg_step_tie(...)` at the call the compiler branches around the fp64 test in each of the
+// 64 steps, 11 % of KE2c's time at 101 x 2^22.)
+__device__ __forceinline__ bool seg_step_tie(bool tie, float a, float x, float b, float r) {
+    const int er = fexp(r);
+    const double u = __longlong_as_double((long long)((uint64_t)(std::max(er, 1) - 150 + 1023) << 52));
+    const double res = fabs(fma((double)a, (double)x, (double)b - (double)r));
+    return tie || res == 0.5 * u || res == 0.25 * u || (b != 0.0f && er - fexp(b) > 28);
 }
 
-__global__ void __launch_bounds__(256)
-eden_segchain_kernel(const float* __restrict__ v, int64_t D, const float* __restrict__ g, float* __restrict__ e,
-                     int32_t* __restrict__ kind, int32_t* __restrict__ tabcnt, int32_t* __restrict__ tabseg, int cap) {
-    __shared__ __attribute__((aligned(16))) float s[kSegPerWG * kSegPad];
-    const int tid = threadIdx.x;
-    const int64_t client = blockIdx.y;
-    const int64_t K = D / kSegBlock;
-    const int64_t seg0 = (int64_t)blockIdx.x * kSegPerWG;
-    seg_stage(v, D, client, seg0, s, tid);
-    __syncthreads();
-    const int sl = tid >> 3, l = tid & 7;
-    const int64_t idx = (client * 8 + l) * K + seg0 + sl;
-    const float* row = s + sl * kSegPad + l;
-    const float g0 = g[idx];
-    float b = g0;
-    bool tie = false;
-#pragma unroll 16
-    for (int i = 0; i < kSegSteps; ++i) {                 // (unrolled: LDS reads ahead of the chain)
-        const float x = row[8 * i];
-        const float r = fmaf(x, x, b);
-        // (b + x*x) - r exactly (fp64: b - r is exact when their exponents are within 28, and
-        // the fma returns the residual exactly whenever it is one of the values tested): a
-        // midpoint is half a grid step, u/2, or u/4 just below a power of two
-        const int er = fexp(r);
-        const double u = __longlong_as_double((long long)((uint64_t)(std::max(er, 1) - 150 + 1023) << 52));
-        const double res = fabs(fma((double)x, (double)x, (double)b - (double)r));
-        tie = tie || res == 0.5 * u || res == 0.25 * u || (b != 0.0f && er - fexp(b) > 28);
-        b = r;
-    }
+// The listing rule of a segment whose guess chain ran g0 -> b: its kind, 0 when every start near
+// g0 translates by b - g0, else slot + 1 of the table it is given in tabseg (code: the segment's),
+// or -1 when the client's `cap` tables are taken (the walk then runs its steps)
+__device__ __forceinline__ int32_t seg_classify(float g0, float b, bool tie, int64_t client, int32_t code, int cap,
+                                                int32_t* __restrict__ tabcnt, int32_t* __restrict__ tabseg) {
     const int eg = fexp(g0);
     const bool finite = eg < 255 && fexp(b) < 255;
     const bool cross = fexp(b) != eg;
     const bool near_bottom = eg > 0 && (fbits(g0) & 0x7FFFFFu) < (uint32_t)(kSegTab / 2);
     const bool near_top = !cross && (((uint32_t)(eg + 1) << 23) - fbits(b)) <= (uint32_t)(kSegTab / 2);
-    int32_t k = 0;
-    if (!finite || cross || tie || near_bottom || near_top) {
-        const int slot = atomicAdd(&tabcnt[client], 1);
-        if (slot < cap) {
-            k = slot + 1;
-            tabseg[client * cap + slot] = (int32_t)((seg0 + sl) * 8 + l);
-        } else {
-            k = -1;                                    // no table: KE2d runs its steps
-        }
-    }
-    e[idx] = b;
-    kind[idx] = k;
+    if (finite && !cross && !tie && !near_bottom && !near_top) return 0;
+    const int slot = atomicAdd(&tabcnt[client], 1);
+    if (slot >= cap) return -1;
+    tabseg[client * cap + slot] = code;
+    return slot + 1;
 }
 
-__global__ void __launch_bounds__(256)
-eden_segtab_kernel(const float* __restrict__ v, int64_t D, const float* __restrict__ g, const int32_t* __restrict__ tabcnt,
-                   const int32_t* __restrict__ tabseg, float* __restrict__ tab, int cap) {
-    __shared__ float xs[kSegSteps];
+// KE2t / KE4t, one workgroup per (slot, client): the listed segment's chain from each of the
+// kSegTab f32 starts whose bit patterns surround its guess's (row: the client's vector)
+template <class Term>
+__device__ __forceinline__ void seg_tab_body(const Term& term, const float* __restrict__ row, int64_t K,
+                                             const float* __restrict__ g, const int32_t* __restrict__ tabcnt,
+                                             const int32_t* __restrict__ tabseg, float* __restrict__ tab, int cap) {
+    __shared__ float2 xa[kSegSteps];                                     // a step's (x, factor): one LDS read
     const int64_t client = blockIdx.y;
     const int slot = blockIdx.x;
     if (slot >= std::min(tabcnt[client], cap)) return;                   // uniform
     const int tid = threadIdx.x;
-    const int32_t code = tabseg[client * cap + slot];
-    const int64_t seg = code >> 3;
-    const int l = code & 7;
-    const int64_t K = D / kSegBlock;
-    if (tid < kSegSteps) xs[tid] = v[client * D + 8 * (seg * kSegSteps + tid) + l];
+    const uint32_t code = (uint32_t)tabseg[client * cap + slot];
+    const int64_t s = code / Term::kChains;
+    const int l = (int)(code % Term::kChains);
+    if (tid < kSegSteps) {
+        const int64_t at = Term::index(s, tid, l);
+        const float x = row[at];
+        xa[tid] = make_float2(x, term.factor(x, at));
+    }
     __syncthreads();
-    const int64_t gb = fbits(g[(client * 8 + l) * K + seg]);
+    const int64_t gb = fbits(g[(client * Term::kChains + l) * K + s]);
     constexpr int kPer = kSegTab / 256;
     float a[kPer];
 #pragma unroll
@@ -1269,27 +1228,25 @@ eden_segtab_kernel(const float* __restrict__ v, int64_t D, const float* __restri
         a[k] = sb < 0 ? __uint_as_float(0x7FC00000u) : __uint_as_float((uint32_t)sb);   // (never looked up)
     }
     for (int i = 0; i < kSegSteps; ++i) {
-        const float x = xs[i];
+        const float2 t = xa[i];
 #pragma unroll
-        for (int k = 0; k < kPer; ++k) a[k] = fmaf(x, x, a[k]);
+        for (int k = 0; k < kPer; ++k) a[k] = fmaf(t.y, t.x, a[k]);
     }
     float* out = tab + ((int64_t)client * cap + slot) * kSegTab;
 #pragma unroll
     for (int k = 0; k < kPer; ++k) out[tid + 256 * k] = a[k];
 }
 
-// one workgroup per client, wave l walks torch lane l's chain.  A wave holds kWalkChunks
-// chunks of 64 segments in registers (lane j: segment 64 q + j of chunk q) and loads the next
-// tile of chunks while it walks this one.
+// KE2d / KE4d: one wave walks chain l of `client` through its K segments from 0 and returns the
+// chain's end (wave-uniform).  The wave holds kWalkChunks chunks of 64 segments in registers
+// (lane j: segment 64 q + j of chunk q) and loads the next tile of chunks while it walks this one.
 constexpr int kWalkChunks = 8;
-__global__ void __launch_bounds__(512)
-eden_segwalk_kernel(const float* __restrict__ v, int64_t D, const float* __restrict__ g, const float* __restrict__ e,
-                    const int32_t* __restrict__ kind, const float* __restrict__ tab, float* __restrict__ nrm, int cap) {
-    __shared__ float accs[8];
-    const int tid = threadIdx.x, lane = tid & (kWave - 1), l = tid / kWave;
-    const int64_t client = blockIdx.x;
-    const int64_t K = D / kSegBlock;
-    const int64_t base = (client * 8 + l) * K;
+template <class Term>
+__device__ __forceinline__ float seg_walk(const Term& term, const float* __restrict__ row, int64_t K, int64_t client, int l,
+                                          const float* __restrict__ g, const float* __restrict__ e,
+                                          const int32_t* __restrict__ kind, const float* __restrict__ tab, int cap,
+                                          int lane) {
+    const int64_t base = (client * Term::kChains + l) * K;
     float cg[kWalkChunks], ce[kWalkChunks], ng[kWalkChunks] = {}, ne[kWalkChunks] = {};
     int32_t ck[kWalkChunks], nk[kWalkChunks] = {};
     auto fetch = [&](int64_t tile, float (&fg)[kWalkChunks], float (&fe)[kWalkChunks], int32_t (&fk)[kWalkChunks]) {
@@ -1339,11 +1296,14 @@ eden_segwalk_kernel(const float* __restrict__ v, int64_t D, const float* __restr
                 done = true;
             }
         }
-        if (!done) {
-            const float x = v[client * D + 8 * (s0 * kSegSteps + lane) + l];
+        if (!done) {                                   // lane i loads step i's factors
+            const int64_t at = Term::index(s0, lane, l);
+            const float x = row[at];
+            const float a = term.factor(x, at);
             for (int i = 0; i < kSegSteps; ++i) {
                 const float xi = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)fbits(x), i));
-                A = fmaf(xi, xi, A);
+                const float ai = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)fbits(a), i));
+                A = fmaf(ai, xi, A);
             }
         }
         s0 += 1;
@@ -1365,6 +1325,94 @@ eden_segwalk_kernel(const float* __restrict__ v, int64_t D, const float* __restr
             ck[q] = nk[q];
         }
     }
+    return A;
+}
+
+// KE2b / KE4b, one workgroup per (chain, client) of L chains: the exclusive prefix of the
+// chain's K segment sums, in rounds of 1024 (4 per thread, coalesced); chain 0's workgroup
+// zeroes the table count
+template <int L>
+__global__ void __launch_bounds__(256)
+eden_segscan_kernel(const double* __restrict__ segsum, int64_t K, float* __restrict__ g, int32_t* __restrict__ tabcnt) {
+    __shared__ double wsum[256 / kWave];
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wid = tid / kWave;
+    const int l = blockIdx.x;
+    const int64_t client = blockIdx.y;
+    if (tid == 0 && l == 0) tabcnt[client] = 0;
+    const double* src = segsum + (client * L + l) * K;
+    float* dst = g + (client * L + l) * K;
+    double carry = 0.0;
+    for (int64_t r0 = 0; r0 < K; r0 += 1024) {
+        double x[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int64_t i = r0 + 4 * tid + k;
+            x[k] = i < K ? src[i] : 0.0;
+        }
+        const double t = (x[0] + x[1]) + (x[2] + x[3]);
+        const double incl = wave_incl_scan(t, lane);
+        if (lane == kWave - 1) wsum[wid] = incl;
+        __syncthreads();
+        double run = carry + wave_prev(incl), tot = carry;
+#pragma unroll
+        for (int w = 0; w < 256 / kWave; ++w) {
+            if (w < wid) run += wsum[w];
+            tot += wsum[w];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int64_t i = r0 + 4 * tid + k;
+            if (i < K) dst[i] = (float)run;
+            run += x[k];
+        }
+        carry = tot;
+    }
+}
+
+// KE2c: thread (segment, lane) runs its segment's 64 steps from the guess, out of LDS
+__global__ void __launch_bounds__(256)
+eden_segchain_kernel(const float* __restrict__ v, int64_t D, const float* __restrict__ g, float* __restrict__ e,
+                     int32_t* __restrict__ kind, int32_t* __restrict__ tabcnt, int32_t* __restrict__ tabseg, int cap) {
+    __shared__ __attribute__((aligned(16))) float s[kSegPerWG * kSegPad];
+    const int tid = threadIdx.x;
+    const int64_t client = blockIdx.y;
+    const int64_t K = D / kSegBlock;
+    const int64_t seg0 = (int64_t)blockIdx.x * kSegPerWG;
+    seg_stage(v, D, client, seg0, s, tid);
+    __syncthreads();
+    const int sl = tid >> 3, l = tid & 7;
+    const int64_t idx = (client * 8 + l) * K + seg0 + sl;
+    const float* row = s + sl * kSegPad + l;
+    const float g0 = g[idx];
+    float b = g0;
+    bool tie = false;
+#pragma unroll 16
+    for (int i = 0; i < kSegSteps; ++i) {                 // (unrolled: LDS reads ahead of the chain)
+        const float x = row[8 * i];
+        const float r = fmaf(x, x, b);
+        tie = seg_step_tie(tie, x, x, b, r);
+        b = r;
+    }
+    e[idx] = b;
+    kind[idx] = seg_classify(g0, b, tie, client, (int32_t)((seg0 + sl) * 8 + l), cap, tabcnt, tabseg);
+}
+
+__global__ void __launch_bounds__(256)
+eden_segtab_kernel(const float* __restrict__ v, int64_t D, const float* __restrict__ g, const int32_t* __restrict__ tabcnt,
+                   const int32_t* __restrict__ tabseg, float* __restrict__ tab, int cap) {
+    seg_tab_body(NormTerm{}, v + (int64_t)blockIdx.y * D, D / kSegBlock, g, tabcnt, tabseg, tab, cap);
+}
+
+// KE2d: one workgroup per client, wave l walks torch lane l's chain; the lanes are then added
+// in order as in KE2
+__global__ void __launch_bounds__(512)
+eden_segwalk_kernel(const float* __restrict__ v, int64_t D, const float* __restrict__ g, const float* __restrict__ e,
+                    const int32_t* __restrict__ kind, const float* __restrict__ tab, float* __restrict__ nrm, int cap) {
+    __shared__ float accs[8];
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), l = tid / kWave;
+    const int64_t client = blockIdx.x;
+    const float A = seg_walk(NormTerm{}, v + client * D, D / kSegBlock, client, l, g, e, kind, tab, cap, lane);
     if (lane == 0) accs[l] = A;
     __syncthreads();
     if (tid == 0) {
@@ -1682,14 +1730,23 @@ eden_thresh_kernel(const float* __restrict__ nrm, EdenTables tab, float* __restr
     if (lane == 3) thr4[j * 4 + 3] = ok ? 1.f : 0.f;
 }
 
-// KE4a: one tile per workgroup; thread (g, l) sums steps 16 g .. 16 g + 15 of chain l
-// (The KE4s kernels that look at elements come in two instances of one body: FRAC, the fractional
-// rates' `_frac_kernel`, reads each element's table from the client's mask row.)
+// The dot's term (see NormTerm): chain l of 64 runs c[bin(x)] * x over elements 64 i + l of the
+// 4096-element tiles.  The KE4s kernels that look at elements are instances of <FRAC>; the
+// fractional rates' read each element's table from the client's mask row (1 and 2 bits ignore `mask`).
 template <bool FRAC>
-__device__ __forceinline__ void
-dseg_sum_body(const float* __restrict__ v, int64_t D, float sqrtD, const float* __restrict__ nrm,
-              const float* __restrict__ thr4, const EdenTables& tab, uint8_t* __restrict__ bins,
-              double* __restrict__ segsum, const EdenMask& mask) {
+struct DotTerm {
+    static constexpr int kChains = 64;
+    typename DotSel<FRAC>::type de;
+    static __device__ __forceinline__ int64_t index(int64_t s, int i, int l) { return s * kEdenTile + 64 * i + l; }
+    __device__ __forceinline__ float factor(float x, int64_t at) const { return cent_at(de, x, at); }
+};
+
+// KE4a: one tile per workgroup; thread (g, l) sums steps 16 g .. 16 g + 15 of chain l
+template <bool FRAC>
+__global__ void __launch_bounds__(256)
+eden_dseg_sum_kernel(const float* __restrict__ v, int64_t D, float sqrtD, const float* __restrict__ nrm,
+                     const float* __restrict__ thr4, EdenTables tab, uint8_t* __restrict__ bins,
+                     double* __restrict__ segsum, EdenMask mask) {
     __shared__ double part[4][64];
     const int tid = threadIdx.x, l = tid & 63, g = tid >> 6;
     const int64_t client = blockIdx.y, k = blockIdx.x, K = D / kEdenTile;
@@ -1711,400 +1768,65 @@ dseg_sum_body(const float* __restrict__ v, int64_t D, float sqrtD, const float* 
     __syncthreads();
     if (tid < 64) segsum[(client * 64 + l) * K + k] = (part[0][l] + part[1][l]) + (part[2][l] + part[3][l]);
 }
-__global__ void __launch_bounds__(256)
-eden_dseg_sum_kernel(const float* __restrict__ v, int64_t D, float sqrtD, const float* __restrict__ nrm,
-                     const float* __restrict__ thr4, EdenTables tab, uint8_t* __restrict__ bins,
-                     double* __restrict__ segsum) {
-    dseg_sum_body<false>(v, D, sqrtD, nrm, thr4, tab, bins, segsum, EdenMask{});
-}
-__global__ void __launch_bounds__(256)
-eden_dseg_sum_frac_kernel(const float* __restrict__ v, int64_t D, float sqrtD, const float* __restrict__ nrm,
-                          const float* __restrict__ thr4, EdenTables tab, uint8_t* __restrict__ bins,
-                          double* __restrict__ segsum, EdenMask mask) {
-    dseg_sum_body<true>(v, D, sqrtD, nrm, thr4, tab, bins, segsum, mask);
-}
 
-// KE4b: exclusive prefix per (chain, client) of its K segment sums (the norm's scan, 64 chains)
-template <int L>
-__global__ void __launch_bounds__(256)
-eden_segscan_l_kernel(const double* __restrict__ segsum, int64_t K, float* __restrict__ g, int32_t* __restrict__ tabcnt) {
-    __shared__ double wsum[256 / kWave];
-    const int tid = threadIdx.x, lane = tid & (kWave - 1), wid = tid / kWave;
-    const int l = blockIdx.x;
-    const int64_t client = blockIdx.y;
-    if (tid == 0 && l == 0) tabcnt[client] = 0;
-    const double* src = segsum + (client * L + l) * K;
-    float* dst = g + (client * L + l) * K;
-    double carry = 0.0;
-    for (int64_t r0 = 0; r0 < K; r0 += 1024) {
-        double xs[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int64_t i = r0 + 4 * tid + q;
-            xs[q] = i < K ? src[i] : 0.0;
-        }
-        const double t = (xs[0] + xs[1]) + (xs[2] + xs[3]);
-        const double incl = wave_incl_scan(t, lane);
-        if (lane == kWave - 1) wsum[wid] = incl;
-        __syncthreads();
-        double run = carry + wave_prev(incl), tot = carry;
-#pragma unroll
-        for (int w = 0; w < 256 / kWave; ++w) {
-            if (w < wid) run += wsum[w];
-            tot += wsum[w];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int64_t i = r0 + 4 * tid + q;
-            if (i < K) dst[i] = (float)run;
-            run += xs[q];
-        }
-        carry = tot;
-    }
-}
-
-// KE4c: thread (tile k, chain l) runs its segment's 64 steps from the guess (the KE2c tests)
+// KE4c: thread (tile k, chain l) runs its segment's 64 steps from the guess, out of memory
 template <bool FRAC>
-__device__ __forceinline__ void
-dseg_chain_body(const float* __restrict__ v, int64_t D, float sqrtD, const float* __restrict__ nrm,
-                const float* __restrict__ thr4, const EdenTables& tab, const float* __restrict__ g,
-                float* __restrict__ e, int32_t* __restrict__ kind, int32_t* __restrict__ tabcnt,
-                int32_t* __restrict__ tabseg, int cap, const EdenMask& mask) {
+__global__ void __launch_bounds__(256)
+eden_dseg_chain_kernel(const float* __restrict__ v, int64_t D, float sqrtD, const float* __restrict__ nrm,
+                       const float* __restrict__ thr4, EdenTables tab, const float* __restrict__ g,
+                       float* __restrict__ e, int32_t* __restrict__ kind, int32_t* __restrict__ tabcnt,
+                       int32_t* __restrict__ tabseg, int cap, EdenMask mask) {
     const int tid = threadIdx.x, l = tid & 63;
     const int64_t client = blockIdx.y, K = D / kEdenTile;
     const int64_t k = (int64_t)blockIdx.x * kDSegTiles + (tid >> 6);
-    const typename DotSel<FRAC>::type de = DotSel<FRAC>::make(thr4, nrm, client, sqrtD, tab, mask, D);
-    const float* t = v + client * D + k * kEdenTile + l;
+    const DotTerm<FRAC> term{DotSel<FRAC>::make(thr4, nrm, client, sqrtD, tab, mask, D)};
+    const float* row = v + client * D;
     const int64_t idx = (client * 64 + l) * K + k;
     const float g0 = g[idx];
     float b = g0;
     bool tie = false;
 #pragma unroll 16
     for (int i = 0; i < kSegSteps; ++i) {
-        const float x = t[64 * i];
-        const float c = cent_at(de, x, k * kEdenTile + l + 64 * i);
+        const int64_t at = term.index(k, i, l);
+        const float x = row[at];
+        const float c = term.factor(x, at);
         // a negative product (a tiny v whose quotient underflowed into the lowest bin) breaks
         // the chain's monotonicity: list the segment (its table or its steps are sequential)
         tie = tie || (((fbits(c) ^ fbits(x)) >> 31) && x != 0.0f && c != 0.0f);
         const float r = fmaf(c, x, b);
-        // (b + c*x) - r exactly: a midpoint is u/2, or u/4 just below a power of two (KE2c)
-        const int er = fexp(r);
-        const double u = __longlong_as_double((long long)((uint64_t)(std::max(er, 1) - 150 + 1023) << 52));
-        const double res = fabs(fma((double)c, (double)x, (double)b - (double)r));
-        tie = tie || res == 0.5 * u || res == 0.25 * u || (b != 0.0f && er - fexp(b) > 28);
+        tie = seg_step_tie(tie, c, x, b, r);
         b = r;
     }
-    const int eg = fexp(g0);
-    const bool finite = eg < 255 && fexp(b) < 255;
-    const bool cross = fexp(b) != eg;
-    const bool near_bottom = eg > 0 && (fbits(g0) & 0x7FFFFFu) < (uint32_t)(kSegTab / 2);
-    const bool near_top = !cross && (((uint32_t)(eg + 1) << 23) - fbits(b)) <= (uint32_t)(kSegTab / 2);
-    int32_t kk = 0;
-    if (!finite || cross || tie || near_bottom || near_top) {
-        const int slot = atomicAdd(&tabcnt[client], 1);
-        if (slot < cap) {
-            kk = slot + 1;
-            tabseg[client * cap + slot] = (int32_t)(k * 64 + l);
-        } else {
-            kk = -1;                                     // no table: KE4d runs its steps
-        }
-    }
     e[idx] = b;
-    kind[idx] = kk;
-}
-__global__ void __launch_bounds__(256)
-eden_dseg_chain_kernel(const float* __restrict__ v, int64_t D, float sqrtD, const float* __restrict__ nrm,
-                       const float* __restrict__ thr4, EdenTables tab, const float* __restrict__ g,
-                       float* __restrict__ e, int32_t* __restrict__ kind, int32_t* __restrict__ tabcnt,
-                       int32_t* __restrict__ tabseg, int cap) {
-    dseg_chain_body<false>(v, D, sqrtD, nrm, thr4, tab, g, e, kind, tabcnt, tabseg, cap, EdenMask{});
-}
-__global__ void __launch_bounds__(256)
-eden_dseg_chain_frac_kernel(const float* __restrict__ v, int64_t D, float sqrtD, const float* __restrict__ nrm,
-                            const float* __restrict__ thr4, EdenTables tab, const float* __restrict__ g,
-                            float* __restrict__ e, int32_t* __restrict__ kind, int32_t* __restrict__ tabcnt,
-                            int32_t* __restrict__ tabseg, int cap, EdenMask mask) {
-    dseg_chain_body<true>(v, D, sqrtD, nrm, thr4, tab, g, e, kind, tabcnt, tabseg, cap, mask);
+    kind[idx] = seg_classify(g0, b, tie, client, (int32_t)(k * 64 + l), cap, tabcnt, tabseg);
 }
 
-// KE4t: the listed segment's chain from each of the kSegTab starts around its guess
-// EDIT TOGETHER with eden_dseg_tab_kernel below (the same text; see the note there).
+// KE4t
 template <bool FRAC>
-__device__ __forceinline__ void
-dseg_tab_body(const float* __restrict__ v, int64_t D, float sqrtD, const float* __restrict__ nrm,
-              const float* __restrict__ thr4, const EdenTables& tab, const float* __restrict__ g,
-              const int32_t* __restrict__ tabcnt, const int32_t* __restrict__ tabseg, float* __restrict__ tabv,
-              int cap, const EdenMask& mask) {
-    __shared__ float xs[kSegSteps], cs_[kSegSteps];
-    const int64_t client = blockIdx.y;
-    const int slot = blockIdx.x;
-    if (slot >= std::min(tabcnt[client], cap)) return;                   // uniform
-    const int tid = threadIdx.x;
-    const int32_t code = tabseg[client * cap + slot];
-    const int64_t k = code >> 6;
-    const int l = code & 63;
-    const int64_t K = D / kEdenTile;
-    if (tid < kSegSteps) {
-        const typename DotSel<FRAC>::type de = DotSel<FRAC>::make(thr4, nrm, client, sqrtD, tab, mask, D);
-        const float x = v[client * D + k * kEdenTile + 64 * tid + l];
-        xs[tid] = x;
-        cs_[tid] = cent_at(de, x, k * kEdenTile + 64 * tid + l);
-    }
-    __syncthreads();
-    const int64_t gb = fbits(g[(client * 64 + l) * K + k]);
-    constexpr int kPer = kSegTab / 256;
-    float a[kPer];
-#pragma unroll
-    for (int q = 0; q < kPer; ++q) {
-        const int64_t sb = gb + tid + 256 * q - kSegTab / 2;
-        a[q] = sb < 0 ? __uint_as_float(0x7FC00000u) : __uint_as_float((uint32_t)sb);   // (never looked up)
-    }
-    for (int i = 0; i < kSegSteps; ++i) {
-        const float x = xs[i], c = cs_[i];
-#pragma unroll
-        for (int q = 0; q < kPer; ++q) a[q] = fmaf(c, x, a[q]);
-    }
-    float* out = tabv + ((int64_t)client * cap + slot) * kSegTab;
-#pragma unroll
-    for (int q = 0; q < kPer; ++q) out[tid + 256 * q] = a[q];
-}
-// EDIT TOGETHER: eden_dseg_tab_kernel below and dseg_tab_body above are one text twice.  The kernel is kept as it
-// was, since as a wrapper of the body its registers were allocated differently and the 1- and 2-bit
-// instances are to stay byte-identical; the body serves the fractional instance alone.  Every fix to
-// one (a bound, an index, a load or store form) goes into the other: the body differs from the kernel
-// only where it reads `mask` (tools/kernel_table.py shows whether the kernel's code moved).
 __global__ void __launch_bounds__(256)
 eden_dseg_tab_kernel(const float* __restrict__ v, int64_t D, float sqrtD, const float* __restrict__ nrm,
                      const float* __restrict__ thr4, EdenTables tab, const float* __restrict__ g,
                      const int32_t* __restrict__ tabcnt, const int32_t* __restrict__ tabseg, float* __restrict__ tabv,
-                     int cap) {
-    __shared__ float xs[kSegSteps], cs_[kSegSteps];
+                     int cap, EdenMask mask) {
     const int64_t client = blockIdx.y;
-    const int slot = blockIdx.x;
-    if (slot >= std::min(tabcnt[client], cap)) return;                   // uniform
-    const int tid = threadIdx.x;
-    const int32_t code = tabseg[client * cap + slot];
-    const int64_t k = code >> 6;
-    const int l = code & 63;
-    const int64_t K = D / kEdenTile;
-    if (tid < kSegSteps) {
-        const DotElem de = dot_elem(thr4, nrm, client, sqrtD, tab);
-        const float x = v[client * D + k * kEdenTile + 64 * tid + l];
-        xs[tid] = x;
-        cs_[tid] = de.cent(x);
-    }
-    __syncthreads();
-    const int64_t gb = fbits(g[(client * 64 + l) * K + k]);
-    constexpr int kPer = kSegTab / 256;
-    float a[kPer];
-#pragma unroll
-    for (int q = 0; q < kPer; ++q) {
-        const int64_t sb = gb + tid + 256 * q - kSegTab / 2;
-        a[q] = sb < 0 ? __uint_as_float(0x7FC00000u) : __uint_as_float((uint32_t)sb);   // (never looked up)
-    }
-    for (int i = 0; i < kSegSteps; ++i) {
-        const float x = xs[i], c = cs_[i];
-#pragma unroll
-        for (int q = 0; q < kPer; ++q) a[q] = fmaf(c, x, a[q]);
-    }
-    float* out = tabv + ((int64_t)client * cap + slot) * kSegTab;
-#pragma unroll
-    for (int q = 0; q < kPer; ++q) out[tid + 256 * q] = a[q];
-}
-__global__ void __launch_bounds__(256)
-eden_dseg_tab_frac_kernel(const float* __restrict__ v, int64_t D, float sqrtD, const float* __restrict__ nrm,
-                          const float* __restrict__ thr4, EdenTables tab, const float* __restrict__ g,
-                          const int32_t* __restrict__ tabcnt, const int32_t* __restrict__ tabseg,
-                          float* __restrict__ tabv, int cap, EdenMask mask) {
-    dseg_tab_body<true>(v, D, sqrtD, nrm, thr4, tab, g, tabcnt, tabseg, tabv, cap, mask);
+    const DotTerm<FRAC> term{DotSel<FRAC>::make(thr4, nrm, client, sqrtD, tab, mask, D)};
+    seg_tab_body(term, v + client * D, D / kEdenTile, g, tabcnt, tabseg, tabv, cap);
 }
 
-// KE4d: wave w of workgroup b walks chain 8 b + w of client blockIdx.y (KE2d's walk); the
-// chain's end goes to acc64[client][chain]
-// EDIT TOGETHER with eden_dseg_walk_kernel below (the same text; see the note there).
+// KE4d: wave w of workgroup b walks chain 8 b + w of client blockIdx.y; the chain's end goes
+// to acc64[client][chain]
 template <bool FRAC>
-__device__ __forceinline__ void
-dseg_walk_body(const float* __restrict__ v, int64_t D, float sqrtD, const float* __restrict__ nrm,
-               const float* __restrict__ thr4, const EdenTables& tab, const float* __restrict__ g,
-               const float* __restrict__ e, const int32_t* __restrict__ kind, const float* __restrict__ tabv,
-               float* __restrict__ acc64, int cap, const EdenMask& mask) {
-    const int tid = threadIdx.x, lane = tid & (kWave - 1);
-    const int l = blockIdx.x * 8 + tid / kWave;
-    const int64_t client = blockIdx.y;
-    const int64_t K = D / kEdenTile;
-    const int64_t base = (client * 64 + l) * K;
-    const typename DotSel<FRAC>::type de = DotSel<FRAC>::make(thr4, nrm, client, sqrtD, tab, mask, D);
-    float cg[kWalkChunks], ce[kWalkChunks], ng[kWalkChunks] = {}, ne[kWalkChunks] = {};
-    int32_t ck[kWalkChunks], nk[kWalkChunks] = {};
-    auto fetch = [&](int64_t tile, float (&fg)[kWalkChunks], float (&fe)[kWalkChunks], int32_t (&fk)[kWalkChunks]) {
-#pragma unroll
-        for (int q = 0; q < kWalkChunks; ++q) {
-            const int64_t s = (tile * kWalkChunks + q) * kWave + lane;
-            fg[q] = s < K ? g[base + s] : 0.0f;
-            fe[q] = s < K ? e[base + s] : 0.0f;
-            fk[q] = s < K ? kind[base + s] : 0;
-        }
-    };
-    float A = 0.0f;                                    // wave-uniform
-    int64_t s0 = 0;
-    auto step = [&](int64_t c, float sg, float se, int32_t sk) {
-        const int o = (int)(s0 - c * kWave);
-        const bool inb = lane >= o && c * kWave + lane < K;
-        const bool fin = fexp(sg) < 255 && fexp(se) < 255;
-        const double tau = (inb && fin) ? (double)se - (double)sg : 0.0;   // >= 0: chains never decrease
-        const double Aj = (double)A + wave_prev(wave_incl_scan(tau, lane));
-        const bool span = A > 0.0f && fexp(A) < 255;
-        const double lim = __longlong_as_double((long long)((uint64_t)(std::max(fexp(A), 1) - 127 + 28 + 1023) << 52));
-        const float af = (float)Aj;
-        const float r = af + (float)tau;
-        const bool valid = inb && fin && (lane == o || (span && Aj + tau < lim)) && (double)af == Aj &&
-                           (af == sg || (sk == 0 && fexp(af) == fexp(sg) && fexp(r) == fexp(sg)));
-        const uint64_t bad = __ballot(inb && !valid);
-        const uint64_t inm = __ballot(inb);
-        const int first = bad ? __builtin_ctzll(bad) : 64 - __builtin_clzll(inm);
-        if (first > o) {
-            const float res = af == sg ? se : r;
-            A = __shfl(res, first - 1, kWave);
-            s0 = c * kWave + first;
-            return;
-        }
-        const int32_t kk = __shfl(sk, o, kWave);
-        const float gg = __shfl(sg, o, kWave);
-        bool done = false;
-        if (kk > 0) {
-            const int64_t dd = (int64_t)fbits(A) - (int64_t)fbits(gg) + kSegTab / 2;
-            if (dd >= 0 && dd < kSegTab) {
-                A = tabv[((int64_t)client * cap + (kk - 1)) * kSegTab + dd];
-                done = true;
-            }
-        }
-        if (!done) {
-            const float x = v[client * D + s0 * kEdenTile + 64 * lane + l];
-            const float c = cent_at(de, x, s0 * kEdenTile + 64 * lane + l);
-            for (int i = 0; i < kSegSteps; ++i) {
-                const float xi = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)fbits(x), i));
-                const float ci = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)fbits(c), i));
-                A = fmaf(ci, xi, A);
-            }
-        }
-        s0 += 1;
-    };
-    fetch(0, cg, ce, ck);
-    const int64_t tiles = (K + kWalkChunks * kWave - 1) / (kWalkChunks * kWave);
-    for (int64_t t = 0; t < tiles; ++t) {
-        if (t + 1 < tiles) fetch(t + 1, ng, ne, nk);
-#pragma unroll
-        for (int q = 0; q < kWalkChunks; ++q) {
-            const int64_t c = t * kWalkChunks + q;
-            const int64_t cend = std::min<int64_t>(K, (c + 1) * kWave);
-            while (s0 < cend) step(c, cg[q], ce[q], ck[q]);
-        }
-#pragma unroll
-        for (int q = 0; q < kWalkChunks; ++q) {
-            cg[q] = ng[q];
-            ce[q] = ne[q];
-            ck[q] = nk[q];
-        }
-    }
-    if (lane == 0) acc64[client * 64 + l] = A;
-}
-// EDIT TOGETHER: eden_dseg_walk_kernel below and dseg_walk_body above are one text twice.  The kernel is kept as it
-// was, since as a wrapper of the body its registers were allocated differently and the 1- and 2-bit
-// instances are to stay byte-identical; the body serves the fractional instance alone.  Every fix to
-// one (a bound, an index, a load or store form) goes into the other: the body differs from the kernel
-// only where it reads `mask` (tools/kernel_table.py shows whether the kernel's code moved).
 __global__ void __launch_bounds__(512)
 eden_dseg_walk_kernel(const float* __restrict__ v, int64_t D, float sqrtD, const float* __restrict__ nrm,
                       const float* __restrict__ thr4, EdenTables tab, const float* __restrict__ g,
                       const float* __restrict__ e, const int32_t* __restrict__ kind, const float* __restrict__ tabv,
-                      float* __restrict__ acc64, int cap) {
+                      float* __restrict__ acc64, int cap, EdenMask mask) {
     const int tid = threadIdx.x, lane = tid & (kWave - 1);
     const int l = blockIdx.x * 8 + tid / kWave;
     const int64_t client = blockIdx.y;
-    const int64_t K = D / kEdenTile;
-    const int64_t base = (client * 64 + l) * K;
-    const DotElem de = dot_elem(thr4, nrm, client, sqrtD, tab);
-    float cg[kWalkChunks], ce[kWalkChunks], ng[kWalkChunks] = {}, ne[kWalkChunks] = {};
-    int32_t ck[kWalkChunks], nk[kWalkChunks] = {};
-    auto fetch = [&](int64_t tile, float (&fg)[kWalkChunks], float (&fe)[kWalkChunks], int32_t (&fk)[kWalkChunks]) {
-#pragma unroll
-        for (int q = 0; q < kWalkChunks; ++q) {
-            const int64_t s = (tile * kWalkChunks + q) * kWave + lane;
-            fg[q] = s < K ? g[base + s] : 0.0f;
-            fe[q] = s < K ? e[base + s] : 0.0f;
-            fk[q] = s < K ? kind[base + s] : 0;
-        }
-    };
-    float A = 0.0f;                                    // wave-uniform
-    int64_t s0 = 0;
-    auto step = [&](int64_t c, float sg, float se, int32_t sk) {
-        const int o = (int)(s0 - c * kWave);
-        const bool inb = lane >= o && c * kWave + lane < K;
-        const bool fin = fexp(sg) < 255 && fexp(se) < 255;
-        const double tau = (inb && fin) ? (double)se - (double)sg : 0.0;   // >= 0: chains never decrease
-        const double Aj = (double)A + wave_prev(wave_incl_scan(tau, lane));
-        const bool span = A > 0.0f && fexp(A) < 255;
-        const double lim = __longlong_as_double((long long)((uint64_t)(std::max(fexp(A), 1) - 127 + 28 + 1023) << 52));
-        const float af = (float)Aj;
-        const float r = af + (float)tau;
-        const bool valid = inb && fin && (lane == o || (span && Aj + tau < lim)) && (double)af == Aj &&
-                           (af == sg || (sk == 0 && fexp(af) == fexp(sg) && fexp(r) == fexp(sg)));
-        const uint64_t bad = __ballot(inb && !valid);
-        const uint64_t inm = __ballot(inb);
-        const int first = bad ? __builtin_ctzll(bad) : 64 - __builtin_clzll(inm);
-        if (first > o) {
-            const float res = af == sg ? se : r;
-            A = __shfl(res, first - 1, kWave);
-            s0 = c * kWave + first;
-            return;
-        }
-        const int32_t kk = __shfl(sk, o, kWave);
-        const float gg = __shfl(sg, o, kWave);
-        bool done = false;
-        if (kk > 0) {
-            const int64_t dd = (int64_t)fbits(A) - (int64_t)fbits(gg) + kSegTab / 2;
-            if (dd >= 0 && dd < kSegTab) {
-                A = tabv[((int64_t)client * cap + (kk - 1)) * kSegTab + dd];
-                done = true;
-            }
-        }
-        if (!done) {
-            const float x = v[client * D + s0 * kEdenTile + 64 * lane + l];
-            const float c = de.cent(x);
-            for (int i = 0; i < kSegSteps; ++i) {
-                const float xi = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)fbits(x), i));
-                const float ci = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)fbits(c), i));
-                A = fmaf(ci, xi, A);
-            }
-        }
-        s0 += 1;
-    };
-    fetch(0, cg, ce, ck);
-    const int64_t tiles = (K + kWalkChunks * kWave - 1) / (kWalkChunks * kWave);
-    for (int64_t t = 0; t < tiles; ++t) {
-        if (t + 1 < tiles) fetch(t + 1, ng, ne, nk);
-#pragma unroll
-        for (int q = 0; q < kWalkChunks; ++q) {
-            const int64_t c = t * kWalkChunks + q;
-            const int64_t cend = std::min<int64_t>(K, (c + 1) * kWave);
-            while (s0 < cend) step(c, cg[q], ce[q], ck[q]);
-        }
-#pragma unroll
-        for (int q = 0; q < kWalkChunks; ++q) {
-            cg[q] = ng[q];
-            ce[q] = ne[q];
-            ck[q] = nk[q];
-        }
-    }
+    const DotTerm<FRAC> term{DotSel<FRAC>::make(thr4, nrm, client, sqrtD, tab, mask, D)};
+    const float A = seg_walk(term, v + client * D, D / kEdenTile, client, l, g, e, kind, tabv, cap, lane);
     if (lane == 0) acc64[client * 64 + l] = A;
-}
-__global__ void __launch_bounds__(512)
-eden_dseg_walk_frac_kernel(const float* __restrict__ v, int64_t D, float sqrtD, const float* __restrict__ nrm,
-                           const float* __restrict__ thr4, EdenTables tab, const float* __restrict__ g,
-                           const float* __restrict__ e, const int32_t* __restrict__ kind, const float* __restrict__ tabv,
-                           float* __restrict__ acc64, int cap, EdenMask mask) {
-    dseg_walk_body<true>(v, D, sqrtD, nrm, thr4, tab, g, e, kind, tabv, acc64, cap, mask);
 }
 
 // KE4f: the 64 chains in MKL's order, scale = f32(nrm * nrm) / dot (AS:335)
