@@ -192,7 +192,11 @@ int uqc_decode(const uint8_t* msg, uint64_t size, int8_t* codes, int64_t d_expec
     const int W = msg[31];
     (void)flags;
     if (magic != TC_MAGIC || ver != 1 || msg[30] != TC_PROB_BITS || (int64_t)d != d_expect || total != size) return -1;
-    if (W != tc_lanes((int64_t)d) || nsym > 256) return -1;
+    if (W != tc_lanes((int64_t)d) || nsym > 256 || (d > 0 && nsym < 2)) return -1;
+    /* nothing below reads past the message: the chunk count is d's, the header fits */
+    const int64_t csz = (int64_t)W * TC_STEPS;
+    const uint64_t hdr = uqc_header_bytes(nsym, nch, W);
+    if ((int64_t)nch != (d > 0 ? ((int64_t)d + csz - 1) / csz : 0) || hdr > size) return -1;
     *m = (int64_t)mm;
     uint32_t f[256] = {0}, cum[257] = {0};
     for (int s = 0; s < nsym; ++s) {
@@ -207,8 +211,10 @@ int uqc_decode(const uint8_t* msg, uint64_t size, int8_t* codes, int64_t d_expec
         for (uint32_t j = cum[s]; j < cum[s + 1]; ++j) lut[j] = (uint8_t)s;
     const uint32_t* wend = (const uint32_t*)(msg + align4(40 + 2 * (uint64_t)nsym));
     const uint32_t* states = wend + nch;
-    const uint16_t* words = (const uint16_t*)(msg + uqc_header_bytes(nsym, nch, W));
-    const int64_t csz = (int64_t)W * TC_STEPS;
+    const uint16_t* words = (const uint16_t*)(msg + hdr);
+    const uint64_t wmax = (size - hdr) / 2;            /* words present */
+    for (int64_t c = 0; c < (int64_t)nch; ++c)
+        if (wend[c] > wmax) return -3;
     for (int64_t c = 0; c < (int64_t)nch; ++c) {
         const int64_t base = c * csz;
         const int64_t len = (int64_t)d - base < csz ? (int64_t)d - base : csz;

@@ -49,6 +49,8 @@ def lib():
         L.uqc_encode.argtypes = [p, i64, i64, f, ctypes.c_int, p]
         L.uqc_decode.restype = ctypes.c_int
         L.uqc_decode.argtypes = [p, ctypes.c_uint64, p, i64, p, p]
+        L.uqc_normalize.restype = None
+        L.uqc_normalize.argtypes = [p, ctypes.c_int, ctypes.c_uint64, p]
         L.uqo_biased_quantize.restype = ctypes.c_int
         L.uqo_biased_quantize.argtypes = [p, p, i64, i64, ctypes.c_int, ctypes.c_int, p, p, p]
         _lib = L
@@ -147,6 +149,14 @@ def biased_quantize(x, m: int, torch_threads: int = 1, tie_mode: int = 0):
     if rc == -2:
         raise RuntimeError("selected index k out of range (AS:660)")
     return out, np.float32(L[0]), int(D[0]), bool(A[0])
+
+
+def codec_normalize(cnt, total: int) -> np.ndarray:
+    """Symbol counts -> the quantized frequencies (sum 2^12) of uqc_normalize."""
+    c = np.ascontiguousarray(cnt, dtype=np.uint32).reshape(-1)
+    f = np.zeros(c.shape[0], np.uint32)
+    lib().uqc_normalize(_ptr(c), c.shape[0], int(total), _ptr(f))
+    return f
 
 
 def codec_encode(codes, m: int, l1: float, exact: bool = False) -> bytes:
