@@ -189,6 +189,26 @@ int uq_test_last_biased_plan(int64_t* plan_out, int32_t cap);
 #define UQ_EDEN_PASS_GENERIC 5
 int uq_test_eden_plan(int32_t op, int64_t n, int64_t dim, int32_t nbits, int32_t mode, int64_t* plan_out, int32_t cap);
 int uq_test_last_eden_plan(int32_t op, int64_t* plan_out, int32_t cap);
+/* Test hooks of the packed message form (uq_eden_compress_packed_f32 / uq_eden_decompress_packed_f32): beside
+ * the EDEN plan above, which such a call records as the u8 call of the same shape does, a packed call names
+ * which kernel writes (compress) or first reads (decompress) the payload rows.  UQ_EDEN_PACKED_PLAN_FIELDS
+ * int64 values, of which min(cap, UQ_EDEN_PACKED_PLAN_FIELDS) are written:
+ *   [0] kind (1, 2, UQ_EDEN_NBITS_FRAC; 0: the op's last call was not a packed one or launched nothing)
+ *   [1] form: UQ_EDEN_PACKED_FUSED (KE4 / KE2+4 and its redo KE4 write payload words; the 4096-element first
+ *       pass reads them) or UQ_EDEN_PACKED_CONVERTER (u8 bins in the workspace and uq_eden_pack_bins' /
+ *       uq_eden_unpack_bins' kernel: the segmented dot, the 16k / generic first passes, every fractional rate)
+ *   [2] P = ceil(D / 32), the words of a plane   [3] the row pitch in words
+ * uq_test_eden_packed_plan: host only (op: UQ_EDEN_OP_COMPRESS or UQ_EDEN_OP_DECOMPRESS), under the current
+ * hooks; uq_test_last_eden_packed_plan: of this thread's last call of that op.
+ * uq_test_set_eden_hooks: process-wide; bit 0 sends every packed call through the u8 bins and the converter,
+ * so that the fused and the fallback form can be compared on the same input.  Returns the previous flags. */
+#define UQ_EDEN_PACKED_PLAN_FIELDS 4
+#define UQ_EDEN_PACKED_NONE 0
+#define UQ_EDEN_PACKED_FUSED 1
+#define UQ_EDEN_PACKED_CONVERTER 2
+int uq_test_set_eden_hooks(int flags);
+int uq_test_eden_packed_plan(int32_t op, int64_t n, int64_t dim, int32_t kind, int64_t* plan_out, int32_t cap);
+int uq_test_last_eden_packed_plan(int32_t op, int64_t* plan_out, int32_t cap);
 /* Host-only, for tests and tools: the MT19937 state (ATen's 624-word array, block-aligned) that
  * `blocks` twists ahead of state624, computed the way the QUIC-FL sender's jump path does it
  * (t^(624 (blocks - 1)) mod phi, phi from Berlekamp-Massey; the correlation with the stream's
@@ -606,6 +626,44 @@ int uq_eden_decompress_frac_f32(const uint8_t* bins, const float* scale, int64_t
 int uq_eden_frac_f32(const float* x, float* out, int64_t n, int64_t dim, const int8_t* signs, const int32_t* sign_row,
                      const uint32_t* sign_bits, const uint32_t* mask_bits, const int32_t* mask_row, float* scale_out,
                      void* ws, size_t ws_bytes, void* stream);
+/* EDEN messages at their rate: the bins bit-packed.  These entry points replace nothing of the reference, which
+ * keeps a message's bins as an int64 tensor (AS:335-350, 352-368; read back at AS:398-411); scale and outputs
+ * are the bits of the u8 entry points above, and the payload is the packing of their bins.
+ * Layout: a client's payload is a row of u32 words, coordinate i of the padded row (D, a power of two) at bit
+ * i % 32 of word i / 32 of a plane (uq_rht_sign_bits' numbering), P = ceil(D / 32) words per plane.
+ *   plane H, words [0, P): the bin (kind 1), bin >> 1 (kind 2), or for kind UQ_EDEN_NBITS_FRAC bin >> 1 where
+ *     the client's mask bit is set and the 1-bit bin where it is clear: above the middle boundary at every rate;
+ *   plane L: none (kind 1); words [P, 2 P) = bin & 1 (kind 2); for a fractional rate the low bits of the
+ *     mask-set coordinates only, in index order: the r-th set bit of the mask row (r from 0) at bit r % 32 of
+ *     word P + r / 32, so the message is D + cnt bits, cnt = popcount(mask row[:D]).
+ * Every bit that names no coordinate is written as 0 (bits >= D of the word when D < 32, bits >= cnt of plane
+ * L's last word, words of the pitch past it).  Row pitch: uq_eden_packed_words (P for kind 1, else 2 P);
+ * payload_bits [n] int64 (or NULL) receives D, 2 D or D + cnt_j.
+ * uq_eden_mask_ranks: ranks [rows][P + 1] u32, the exclusive rank (set bits before it) of each word of a mask row
+ *   (uq_eden_mask_bits) and cnt in the last entry: a pure function of the row, cached with it by callers.
+ * uq_eden_pack_bins / uq_eden_unpack_bins: u8 bins [n][D] <-> payload rows, for any D >= 0; mask_bits,
+ *   mask_ranks and mask_row (NULL: row 0) are read for the fractional kind only.  Unpacking a fractional
+ *   message gives the bins uq_eden_compress_frac_f32 writes (0..3 where the mask is set, 0..1 elsewhere).
+ * uq_eden_compress_packed_f32 / uq_eden_decompress_packed_f32: the _sb / _frac entry points by `kind`, with the
+ *   payload rows in place of bins.  Workspace: uq_eden_packed_workspace_bytes.  One wave per client (KE4), KE2+4
+ *   and the receiver's 4096-element first pass write / read the words themselves at kinds 1 and 2; other shapes
+ *   and the fractional kind go through u8 bins in the workspace and the converters (uq_test_last_eden_packed_plan). */
+int uq_eden_packed_words(int64_t D, int32_t kind, int64_t* pitch_words);
+int uq_eden_packed_workspace_bytes(int64_t n, int64_t dim, int32_t kind, size_t* bytes_out);
+int uq_eden_mask_ranks(const uint32_t* mask_bits, int64_t rows, int64_t D, uint32_t* ranks, void* stream);
+int uq_eden_pack_bins(const uint8_t* bins, int64_t n, int64_t D, int32_t kind, const uint32_t* mask_bits,
+                      const uint32_t* mask_ranks, const int32_t* mask_row, uint32_t* payload, int64_t* payload_bits,
+                      void* stream);
+int uq_eden_unpack_bins(const uint32_t* payload, int64_t n, int64_t D, int32_t kind, const uint32_t* mask_bits,
+                        const uint32_t* mask_ranks, const int32_t* mask_row, uint8_t* bins, void* stream);
+int uq_eden_compress_packed_f32(const float* x, int64_t n, int64_t dim, int32_t kind, const int8_t* signs,
+                                const int32_t* sign_row, const uint32_t* sign_bits, const uint32_t* mask_bits,
+                                const uint32_t* mask_ranks, const int32_t* mask_row, uint32_t* payload,
+                                int64_t* payload_bits, float* scale, void* ws, size_t ws_bytes, void* stream);
+int uq_eden_decompress_packed_f32(const uint32_t* payload, const float* scale, int64_t n, int64_t dim, int32_t kind,
+                                  const int8_t* signs, const int32_t* sign_row, const uint32_t* sign_bits,
+                                  const uint32_t* mask_bits, const uint32_t* mask_ranks, const int32_t* mask_row, float* out,
+                                  void* ws, size_t ws_bytes, void* stream);
 /* torch.norm(v[j], 2) of each row of v [n][D] f32 in torch's CPU order (AS:329: 8 lanes of
  * fma chains, lanes added in order, sqrt), the norm the EDEN entry points use:
  *   mode 1: the sequential chains (one chain per torch lane; what batches above 256 rows use)

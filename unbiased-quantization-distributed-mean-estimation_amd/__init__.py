@@ -15,7 +15,7 @@ from .quantizer import (
 from .codes import TypeCodes, TypeMessages, encode_messages, decode_messages
 from .biased import Type_biased_quantize, biased_quantize, biased_quantize_encode, biased_quantize_mean
 from .eden import (EDEN_quantize_Hadamard, eden_quantize, eden_compress, eden_decompress, EdenMessage, rht_signs,
-                   randomized_hadamard_transform, randomized_inverse_hadamard_transform)
+                   randomized_hadamard_transform, randomized_inverse_hadamard_transform, eden_pack, eden_unpack)
 from .quicfl import (QuicFLReceiver, QuicFLSender, QuicFLMessages, QUICFL_quantize, quicfl_compress,
                      quicfl_decompress, quicfl_decompress_messages, quicfl_quantize, set_tables_prefix)
 from .rand_schemes import Scalar_quantize, DRIVE_quantize_Hadamard, scalar_quantize, drive_quantize, drive_words
@@ -39,7 +39,7 @@ __all__ = [
     "sharded_quantize_mean", "DISTRIBUTIONS", "Suspended", "legacy_draw", "nmse_simulation", "quantize_encode", "decode", "codes_mean",
     "TypeCodes", "Type_biased_quantize", "biased_quantize", "biased_quantize_encode", "biased_quantize_mean",
     "EDEN_quantize_Hadamard", "eden_quantize",
-    "eden_compress", "eden_decompress", "EdenMessage", "rht_signs", "randomized_hadamard_transform",
+    "eden_compress", "eden_decompress", "eden_pack", "eden_unpack", "EdenMessage", "rht_signs", "randomized_hadamard_transform",
     "randomized_inverse_hadamard_transform", "compute_nmse_stats_auto", "data_format", "round_nmse",
     "DMEPipeline", "codes4_fits", "ShardedDME", "TypeMessages", "encode_messages", "decode_messages", "set_output_pool",
 ]

@@ -89,6 +89,19 @@ SIGNATURES = {
     "uq_eden_compress_frac_f32": (ctypes.c_int, [_p, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "uq_eden_decompress_frac_f32": (ctypes.c_int, [_p, _p, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "uq_eden_frac_f32": (ctypes.c_int, [_p, _p, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    # the bit-packed message form
+    "uq_test_set_eden_hooks": (ctypes.c_int, [ctypes.c_int]),
+    "uq_test_eden_packed_plan": (ctypes.c_int, [_i32, _i64, _i64, _i32, _p, _i32]),
+    "uq_test_last_eden_packed_plan": (ctypes.c_int, [_i32, _p, _i32]),
+    "uq_eden_packed_words": (ctypes.c_int, [_i64, _i32, ctypes.POINTER(_i64)]),
+    "uq_eden_packed_workspace_bytes": (ctypes.c_int, [_i64, _i64, _i32, ctypes.POINTER(_sz)]),
+    "uq_eden_mask_ranks": (ctypes.c_int, [_p, _i64, _i64, _p, _p]),
+    # bins | payload, n, D, kind, mask_bits, mask_ranks, mask_row, payload (, payload_bits) | bins, stream
+    "uq_eden_pack_bins": (ctypes.c_int, [_p, _i64, _i64, _i32, _p, _p, _p, _p, _p, _p]),
+    "uq_eden_unpack_bins": (ctypes.c_int, [_p, _i64, _i64, _i32, _p, _p, _p, _p, _p]),
+    # x | payload, scale; n, dim, kind, signs, sign_row, sign_bits, mask_bits, mask_ranks, mask_row, outputs, ws, ws_bytes, stream
+    "uq_eden_compress_packed_f32": (ctypes.c_int, [_p, _i64, _i64, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "uq_eden_decompress_packed_f32": (ctypes.c_int, [_p, _p, _i64, _i64, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "uq_eden_norm_workspace_bytes": (ctypes.c_int, [_i64, _i64, ctypes.POINTER(_sz)]),
     "uq_eden_norm_f32": (ctypes.c_int, [_p, _i64, _i64, _i32, _p, _p, _sz, _p]),
     "uq_rand_workspace_bytes": (ctypes.c_int, [_i64, _i64, ctypes.POINTER(_sz)]),

@@ -5,12 +5,16 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
 
 #include "uq_eden_kernels.h"
 #include "uq_internal.h"
+
+// uq_test_set_eden_hooks (include/uq_dme.h); each packed entry point loads it once, into its plan
+static std::atomic<int> g_eden_hooks{0};
 
 namespace {
 
@@ -121,6 +125,27 @@ EdenPlan eden_plan(int op, int64_t n, int64_t dim, int32_t nbits, int32_t mode) 
 
 thread_local EdenPlan t_last_plan[UQ_EDEN_OPS];      // uq_test_last_eden_plan, per op
 const EdenPlan& record(const EdenPlan& P) { return t_last_plan[P.op] = P; }
+
+// The packed message form (uq_eden_*_packed_f32) of a plan: which kernel writes, or first reads, the payload rows.
+// Fused: KE4 (one wave per client) and KE2+4 with its redo KE4 on the sender, the 4096-element first pass on the
+// receiver, at 1 and 2 bits.  Everything else -- the segmented dot, the 16k / generic first passes, the fractional
+// rates, and every call under test hook bit 0 -- goes through the u8 bins of the workspace and a converter.
+struct PackedPlan {
+    int32_t kind = 0, form = UQ_EDEN_PACKED_NONE;
+    int64_t P = 0, pitch = 0;
+};
+bool packed_kind_ok(int32_t kind) { return kind == 1 || kind == 2 || kind == UQ_EDEN_NBITS_FRAC; }
+PackedPlan packed_plan(const EdenPlan& E, int32_t kind, int hooks) {
+    PackedPlan k;
+    k.kind = kind;
+    k.P = (E.D + 31) / 32;
+    k.pitch = kind == 1 ? k.P : 2 * k.P;
+    const bool fused = E.op == UQ_EDEN_OP_COMPRESS ? E.dot == UQ_EDEN_DOT_ONE_WAVE || E.dot == UQ_EDEN_DOT_FUSED_REDO
+                                                   : E.npass > 0 && E.pass[0].kernel == UQ_EDEN_PASS_LOW4096;
+    k.form = fused && kind != UQ_EDEN_NBITS_FRAC && !(hooks & 1) ? UQ_EDEN_PACKED_FUSED : UQ_EDEN_PACKED_CONVERTER;
+    return k;
+}
+thread_local PackedPlan t_last_packed[2];             // uq_test_last_eden_packed_plan: compress, decompress
 
 // ---- workspace layouts ---------------------------------------------------------------
 // The segmented region's arrays at address r (0: for `total` alone), each on a 256-byte boundary: KE2s uses
@@ -242,6 +267,13 @@ void select_small_k(int k, F&& f) {
     k == 1 ? f(Int<1>{}) : k == 2 ? f(Int<2>{}) : k == 3 ? f(Int<3>{}) : k == 4 ? f(Int<4>{}) : k == 5 ? f(Int<5>{}) : f(Int<6>{});
 }
 
+// the packed instances' launches (defined after the u8 forms')
+int launch_low4096_packed(const FwhtArgs& a, int kind, bool last, dim3 grid, hipStream_t st);
+int launch_normdot1_packed(const float* rot, int64_t n, int64_t D, float sqrtD, const EdenTables& tab, float* nrm,
+                           uint32_t* payload, float* scale, int32_t* redo, hipStream_t st);
+int launch_eden_dotbins_packed(const float* v, int64_t n, int64_t D, float sqrtD, const float* nrm, const EdenTables& tab,
+                               uint32_t* payload, float* scale, hipStream_t st, const int32_t* redo);
+
 FwhtArgs fwht_args(const void* in, const int8_t* signs, const int32_t* sign_row, const uint32_t* sbits,
                    const float* scale, int64_t D, int64_t dim, const EdenTables& tab) {
     const float sqrtD = (float)std::sqrt((double)D);         // np.sqrt(d) -> f32 operand
@@ -253,7 +285,7 @@ FwhtArgs fwht_args(const void* in, const int8_t* signs, const int32_t* sign_row,
 // `buf` and `out` (out == buf: in place; the forward RHT passes its output so that a two-pass
 // transform needs no copy); *result = the buffer holding the result.
 int launch_passes(const EdenPlan& P, FwhtArgs a, int64_t n, float* buf, float* out, hipStream_t st, float** result = nullptr,
-                  const EdenMask* frac = nullptr) {
+                  const EdenMask* frac = nullptr, int packed_kind = 0) {
     float* dst = nullptr;
     for (int i = 0; i < P.npass; ++i) {
         const EdenPass& s = P.pass[i];
@@ -261,6 +293,10 @@ int launch_passes(const EdenPlan& P, FwhtArgs a, int64_t n, float* buf, float* o
         if (i) a.in = dst;
         a.out = dst = P.sender() ? (i % 2 ? out : buf) : (last ? out : buf);
         const dim3 grid(s.gx, (unsigned)n);
+        if (i == 0 && packed_kind) {                     // a.in: payload rows (the plan's packed form is the fused one)
+            if (const int rc = launch_low4096_packed(a, packed_kind, last, grid, st)) return rc;
+            continue;
+        }
         if (i == 0 && frac && P.mode0() == 2) {
             // a fractional receiver's first pass: the plan's kernel for MODE 2, its MODE 3 instance
             // (the table of each bin by the mask rows); never a later pass's kernel
@@ -327,6 +363,7 @@ int eden_front(const EdenCall& c, const float* x, float** rot) {
 template <class F>
 int eden_call(EdenCall& c, int op, bool null_ptr, F&& body) {
     t_last_plan[op] = EdenPlan{};
+    t_last_packed[op == UQ_EDEN_OP_DECOMPRESS] = PackedPlan{};
     if (c.n < 0 || c.dim < 0) return fail(UQ_E_INVALID, "n and dim must be >= 0");
     if (c.n > 65535) return fail(UQ_E_INVALID, "at most 65535 clients per call");
     if (c.dim > ((int64_t)1 << 28)) return fail(UQ_E_INVALID, "dim must be <= 2^28");
@@ -342,7 +379,8 @@ int eden_call(EdenCall& c, int op, bool null_ptr, F&& body) {
 }
 
 // EdenSender.compress: the front, then the bins and the scale's dot in the plan's form (AS:329-335)
-int eden_compress(const EdenCall& c, const float* x, uint8_t* bins, float* scale) {
+// (payload set: the plan's packed form is the fused one, and the kernels that write bins write payload rows)
+int eden_compress(const EdenCall& c, const float* x, uint8_t* bins, float* scale, uint32_t* payload = nullptr) {
     const EdenPlan& P = record(c.P);
     hipStream_t st = (hipStream_t)c.stream;
     float* rot = nullptr;
@@ -355,18 +393,24 @@ int eden_compress(const EdenCall& c, const float* x, uint8_t* bins, float* scale
     int32_t* redo = nullptr;
     if (P.dot == UQ_EDEN_DOT_FUSED_REDO) {
         redo = (int32_t*)c.at(c.w.redo_off);
+        if (payload) {
+            if ((rc = launch_normdot1_packed(rot, c.n, P.D, sqrtD, c.tab, nrm, payload, scale, redo, st))) return rc;
+            return launch_eden_dotbins_packed(rot, c.n, P.D, sqrtD, nrm, c.tab, payload, scale, st, redo);
+        }
         hipLaunchKernelGGL(eden_normdot1_kernel, dim3((unsigned)((c.n + kNormClients - 1) / kNormClients)), dim3(kNDThreads),
                            0, st, rot, c.n, P.D, sqrtD, c.tab, nrm, bins, scale, redo);
         if ((rc = launched("eden_normdot1_kernel launch"))) return rc;
     }
+    if (payload) return launch_eden_dotbins_packed(rot, c.n, P.D, sqrtD, nrm, c.tab, payload, scale, st, redo);
     return launch_eden_dotbins(rot, c.n, P.D, sqrtD, nrm, c.tab, bins, scale, st, redo, P.frac ? &c.mask : nullptr);
 }
 
 // EdenReceiver.decompress (AS:378-413)
-int eden_decompress(const EdenCall& c, const uint8_t* bins, const float* scale, float* out) {
+// (packed_kind 1 or 2: `bins` are payload rows, read by the packed instance of the first pass)
+int eden_decompress(const EdenCall& c, const void* bins, const float* scale, float* out, int packed_kind = 0) {
     const FwhtArgs a = fwht_args(bins, c.signs, c.sign_row, c.sbits, scale, c.P.D, c.dim, c.tab);
     return launch_passes(record(c.P), a, c.n, (float*)c.at(c.w.vec_off), out, (hipStream_t)c.stream, nullptr,
-                         c.P.frac ? &c.mask : nullptr);
+                         c.P.frac ? &c.mask : nullptr, packed_kind);
 }
 
 // The _frac entry points' call: the 2-bit tables, the 1-bit centroids beside the mask rows
@@ -406,6 +450,92 @@ int export_plan(const EdenPlan& P, int64_t* out, int32_t cap) {
     f[23] = P.tab_cap;
     f[24] = P.frac;
     std::copy(f, f + std::min<int32_t>(cap, UQ_EDEN_PLAN_FIELDS), out);
+    return UQ_OK;
+}
+
+// ---- the packed message form -----------------------------------------------------------
+int launch_low4096_packed(const FwhtArgs& a, int kind, bool last, dim3 grid, hipStream_t st) {
+    if (kind == 1 && last) hipLaunchKernelGGL((fwht_low4096_packed_kernel<4, true, true>), grid, dim3(256), 0, st, a);
+    else if (kind == 1) hipLaunchKernelGGL((fwht_low4096_packed_kernel<4, false, false>), grid, dim3(256), 0, st, a);
+    else if (last) hipLaunchKernelGGL((fwht_low4096_packed_kernel<5, true, true>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((fwht_low4096_packed_kernel<5, false, false>), grid, dim3(256), 0, st, a);
+    return launched("fwht_low4096_packed_kernel launch");
+}
+
+int launch_normdot1_packed(const float* rot, int64_t n, int64_t D, float sqrtD, const EdenTables& tab, float* nrm,
+                           uint32_t* payload, float* scale, int32_t* redo, hipStream_t st) {
+    hipLaunchKernelGGL(eden_normdot1_packed_kernel, dim3((unsigned)((n + kNormClients - 1) / kNormClients)), dim3(kNDThreads), 0,
+                       st, rot, n, D, sqrtD, tab, nrm, payload, scale, redo);
+    return launched("eden_normdot1_packed_kernel launch");
+}
+
+int launch_eden_dotbins_packed(const float* v, int64_t n, int64_t D, float sqrtD, const float* nrm, const EdenTables& tab,
+                               uint32_t* payload, float* scale, hipStream_t st, const int32_t* redo) {
+    const dim3 grid((unsigned)((n + kDotWaves - 1) / kDotWaves)), block(64 * kDotWaves);
+    if (tab.nb == 1)
+        hipLaunchKernelGGL(eden_dotbins_packed_kernel<1>, grid, block, 0, st, v, D, sqrtD, nrm, tab, payload, scale, n, redo);
+    else
+        hipLaunchKernelGGL(eden_dotbins_packed_kernel<3>, grid, block, 0, st, v, D, sqrtD, nrm, tab, payload, scale, n, redo);
+    return launched("eden_dotbins_packed_kernel launch");
+}
+
+template <class F>
+void select_kind(int kind, F&& f) {
+    kind == 1 ? f(Int<1>{}) : kind == 2 ? f(Int<2>{}) : f(Int<3>{});
+}
+
+int launch_payload_bits(int64_t n, int64_t D, int kind, const PackRows& r, int64_t* payload_bits, hipStream_t st) {
+    if (!payload_bits) return UQ_OK;
+    hipLaunchKernelGGL(eden_payload_bits_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, D,
+                       kind == UQ_EDEN_NBITS_FRAC ? 3 : kind, r, payload_bits);
+    return launched("eden_payload_bits_kernel launch");
+}
+
+int launch_pack(const uint8_t* bins, int64_t n, int64_t D, int kind, const PackRows& r, uint32_t* payload,
+                int64_t* payload_bits, hipStream_t st) {
+    const int64_t P = (D + 31) / 32, pitch = kind == 1 ? P : 2 * P;
+    select_kind(kind, [&](auto K) {
+        hipLaunchKernelGGL(eden_pack_bins_kernel<K()>, dim3((unsigned)((pitch + 255) / 256), (unsigned)n), dim3(256), 0, st, bins,
+                           D, r, payload);
+    });
+    if (const int rc = launched("eden_pack_bins_kernel launch")) return rc;
+    return launch_payload_bits(n, D, kind, r, payload_bits, st);
+}
+
+int launch_unpack(const uint32_t* payload, int64_t n, int64_t D, int kind, const PackRows& r, uint8_t* bins, hipStream_t st) {
+    const int64_t P = (D + 31) / 32;
+    select_kind(kind, [&](auto K) {
+        hipLaunchKernelGGL(eden_unpack_bins_kernel<K()>, dim3((unsigned)((P + 255) / 256), (unsigned)n), dim3(256), 0, st, payload,
+                           D, r, bins);
+    });
+    return launched("eden_unpack_bins_kernel launch");
+}
+
+// the converters' checks, in their order; then body()
+template <class F>
+int pack_call(int64_t n, int64_t D, int32_t kind, const PackRows& r, bool null_ptr, F&& body) {
+    if (!packed_kind_ok(kind)) return fail(UQ_E_INVALID, "kind must be 1, 2 or UQ_EDEN_NBITS_FRAC");
+    if (n < 0 || D < 0) return fail(UQ_E_INVALID, "n and D must be >= 0");
+    if (n > 65535) return fail(UQ_E_INVALID, "at most 65535 clients per call");
+    if (D > ((int64_t)1 << 28)) return fail(UQ_E_INVALID, "D must be <= 2^28");
+    if (n == 0 || D == 0) return UQ_OK;
+    if (null_ptr) return fail(UQ_E_INVALID, "null pointer");
+    if (kind == UQ_EDEN_NBITS_FRAC && (!r.mask || !r.ranks)) return fail(UQ_E_INVALID, "null mask_bits or mask_ranks");
+    return body();
+}
+
+// The packed entry points' call: the integer rates' or the fractional one (frac_call), and the rank rows' check
+EdenCall packed_call(int64_t n, int64_t dim, int32_t kind, const int8_t* signs, const int32_t* sign_row,
+                     const uint32_t* sign_bits, const uint32_t* mask_bits, const int32_t* mask_row, void* ws, size_t ws_bytes,
+                     void* stream) {
+    if (kind == UQ_EDEN_NBITS_FRAC) return frac_call(n, dim, signs, sign_row, sign_bits, mask_bits, mask_row, ws, ws_bytes, stream);
+    return EdenCall{n, dim, kind, signs, sign_row, sign_bits, ws, ws_bytes, stream};
+}
+
+int export_packed(const PackedPlan& k, int64_t* out, int32_t cap) {
+    if (!out || cap < 0) return fail(UQ_E_INVALID, "null plan output");
+    const int64_t f[UQ_EDEN_PACKED_PLAN_FIELDS] = {k.kind, k.form, k.P, k.pitch};
+    std::copy(f, f + std::min<int32_t>(cap, UQ_EDEN_PACKED_PLAN_FIELDS), out);
     return UQ_OK;
 }
 
@@ -598,6 +728,104 @@ int uq_eden_decompress_f32(const uint8_t* bins, const float* scale, int64_t n, i
 int uq_eden_f32(const float* x, float* out, int64_t n, int64_t dim, int32_t nbits, const int8_t* signs,
                 const int32_t* sign_row, float* scale_out, void* ws, size_t ws_bytes, void* stream) {
     return uq_eden_f32_sb(x, out, n, dim, nbits, signs, sign_row, nullptr, scale_out, ws, ws_bytes, stream);
+}
+
+// ---- the bit-packed message form (it replaces nothing of the reference: AS:335-350 keeps int64 bins) ----
+int uq_test_set_eden_hooks(int flags) { return g_eden_hooks.exchange(flags & 1); }
+
+int uq_test_eden_packed_plan(int32_t op, int64_t n, int64_t dim, int32_t kind, int64_t* plan_out, int32_t cap) {
+    if (op != UQ_EDEN_OP_COMPRESS && op != UQ_EDEN_OP_DECOMPRESS) return fail(UQ_E_INVALID, "op must be compress or decompress");
+    if (!packed_kind_ok(kind)) return fail(UQ_E_INVALID, "kind must be 1, 2 or UQ_EDEN_NBITS_FRAC");
+    if (n < 0 || dim < 0) return fail(UQ_E_INVALID, "n and dim must be >= 0");
+    if (n == 0 || dim == 0) return export_packed(PackedPlan{}, plan_out, cap);
+    return export_packed(packed_plan(eden_plan(op, n, dim, kind, 0), kind, g_eden_hooks.load()), plan_out, cap);
+}
+
+int uq_test_last_eden_packed_plan(int32_t op, int64_t* plan_out, int32_t cap) {
+    if (op != UQ_EDEN_OP_COMPRESS && op != UQ_EDEN_OP_DECOMPRESS) return fail(UQ_E_INVALID, "op must be compress or decompress");
+    return export_packed(t_last_packed[op == UQ_EDEN_OP_DECOMPRESS], plan_out, cap);
+}
+
+int uq_eden_packed_words(int64_t D, int32_t kind, int64_t* pitch_words) {
+    if (!pitch_words) return fail(UQ_E_INVALID, "null pitch_words");
+    if (!packed_kind_ok(kind)) return fail(UQ_E_INVALID, "kind must be 1, 2 or UQ_EDEN_NBITS_FRAC");
+    if (D < 0) return fail(UQ_E_INVALID, "D must be >= 0");
+    const int64_t P = (D + 31) / 32;
+    *pitch_words = kind == 1 ? P : 2 * P;
+    return UQ_OK;
+}
+
+int uq_eden_packed_workspace_bytes(int64_t n, int64_t dim, int32_t kind, size_t* bytes_out) {
+    if (!packed_kind_ok(kind)) return fail(UQ_E_INVALID, "kind must be 1, 2 or UQ_EDEN_NBITS_FRAC");
+    // (the layout's u8 bins region, which uq_eden_f32 uses between its two halves, serves the converter path)
+    return uq_eden_workspace_bytes(n, dim, bytes_out);
+}
+
+int uq_eden_mask_ranks(const uint32_t* mask_bits, int64_t rows, int64_t D, uint32_t* ranks, void* stream) {
+    if (rows < 0 || D < 0) return fail(UQ_E_INVALID, "rows and D must be >= 0");
+    if (rows == 0) return UQ_OK;
+    if (rows > 65535) return fail(UQ_E_INVALID, "at most 65535 rows per call");
+    if (!ranks || (D > 0 && !mask_bits)) return fail(UQ_E_INVALID, "null pointer");
+    hipLaunchKernelGGL(eden_mask_ranks_kernel, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, mask_bits, D, ranks);
+    return launched("eden_mask_ranks_kernel launch");
+}
+
+int uq_eden_pack_bins(const uint8_t* bins, int64_t n, int64_t D, int32_t kind, const uint32_t* mask_bits,
+                      const uint32_t* mask_ranks, const int32_t* mask_row, uint32_t* payload, int64_t* payload_bits,
+                      void* stream) {
+    const PackRows r{mask_bits, mask_ranks, mask_row};
+    return pack_call(n, D, kind, r, !bins || !payload,
+                     [&] { return launch_pack(bins, n, D, kind, r, payload, payload_bits, (hipStream_t)stream); });
+}
+
+int uq_eden_unpack_bins(const uint32_t* payload, int64_t n, int64_t D, int32_t kind, const uint32_t* mask_bits,
+                        const uint32_t* mask_ranks, const int32_t* mask_row, uint8_t* bins, void* stream) {
+    const PackRows r{mask_bits, mask_ranks, mask_row};
+    return pack_call(n, D, kind, r, !bins || !payload,
+                     [&] { return launch_unpack(payload, n, D, kind, r, bins, (hipStream_t)stream); });
+}
+
+int uq_eden_compress_packed_f32(const float* x, int64_t n, int64_t dim, int32_t kind, const int8_t* signs,
+                                const int32_t* sign_row, const uint32_t* sign_bits, const uint32_t* mask_bits,
+                                const uint32_t* mask_ranks, const int32_t* mask_row, uint32_t* payload,
+                                int64_t* payload_bits, float* scale, void* ws, size_t ws_bytes, void* stream) {
+    const int hooks = g_eden_hooks.load();
+    t_last_plan[UQ_EDEN_OP_COMPRESS] = EdenPlan{};
+    t_last_packed[0] = PackedPlan{};
+    if (!packed_kind_ok(kind)) return fail(UQ_E_INVALID, "kind must be 1, 2 or UQ_EDEN_NBITS_FRAC");
+    EdenCall c = packed_call(n, dim, kind, signs, sign_row, sign_bits, mask_bits, mask_row, ws, ws_bytes, stream);
+    const bool null_ptr = !x || !payload || !scale || (kind == UQ_EDEN_NBITS_FRAC && !mask_ranks);
+    return eden_call(c, UQ_EDEN_OP_COMPRESS, null_ptr, [&] {
+        const PackedPlan k = t_last_packed[0] = packed_plan(c.P, kind, hooks);
+        const PackRows r{mask_bits, mask_ranks, mask_row};
+        hipStream_t st = (hipStream_t)stream;
+        if (k.form == UQ_EDEN_PACKED_FUSED) {
+            const int rc = eden_compress(c, x, nullptr, scale, payload);
+            return rc ? rc : launch_payload_bits(n, c.P.D, kind, r, payload_bits, st);
+        }
+        uint8_t* bins = (uint8_t*)c.at(c.w.bins_off);
+        const int rc = eden_compress(c, x, bins, scale);
+        return rc ? rc : launch_pack(bins, n, c.P.D, kind, r, payload, payload_bits, st);
+    });
+}
+
+int uq_eden_decompress_packed_f32(const uint32_t* payload, const float* scale, int64_t n, int64_t dim, int32_t kind,
+                                  const int8_t* signs, const int32_t* sign_row, const uint32_t* sign_bits,
+                                  const uint32_t* mask_bits, const uint32_t* mask_ranks, const int32_t* mask_row, float* out,
+                                  void* ws, size_t ws_bytes, void* stream) {
+    const int hooks = g_eden_hooks.load();
+    t_last_plan[UQ_EDEN_OP_DECOMPRESS] = EdenPlan{};
+    t_last_packed[1] = PackedPlan{};
+    if (!packed_kind_ok(kind)) return fail(UQ_E_INVALID, "kind must be 1, 2 or UQ_EDEN_NBITS_FRAC");
+    EdenCall c = packed_call(n, dim, kind, signs, sign_row, sign_bits, mask_bits, mask_row, ws, ws_bytes, stream);
+    const bool null_ptr = !payload || !scale || !out || (kind == UQ_EDEN_NBITS_FRAC && !mask_ranks);
+    return eden_call(c, UQ_EDEN_OP_DECOMPRESS, null_ptr, [&] {
+        const PackedPlan k = t_last_packed[1] = packed_plan(c.P, kind, hooks);
+        if (k.form == UQ_EDEN_PACKED_FUSED) return eden_decompress(c, payload, scale, out, kind);
+        uint8_t* bins = (uint8_t*)c.at(c.w.bins_off);
+        const int rc = launch_unpack(payload, n, c.P.D, kind, PackRows{mask_bits, mask_ranks, mask_row}, bins, (hipStream_t)stream);
+        return rc ? rc : eden_decompress(c, bins, scale, out);
+    });
 }
 
 }  // extern "C"

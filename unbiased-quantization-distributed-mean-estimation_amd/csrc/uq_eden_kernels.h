@@ -480,6 +480,27 @@ __device__ __forceinline__ void fwht_low4096_body(FwhtArgs a, const EdenMask& ma
             __syncthreads();
 #pragma unroll
             for (int i = 0; i < 16; ++i) v[i] = cent8[(bb[i] & 3u) | (((mw >> i) & 1u) << 2)];   // AS:407-411
+        } else if constexpr (MODE == 4 || MODE == 5) {
+            // the bit-packed message (1 bit: MODE 4, 2 bits: MODE 5): the thread's 16 bins are half a
+            // word of plane H (and of plane L); two lanes read the same word
+            const int64_t Pw = D >> 5;                                             // (D >= 4096 here)
+            const uint32_t* pay = (const uint32_t*)a.in + vec * (MODE == 4 ? Pw : 2 * Pw);
+            const uint32_t h = pay[i0 >> 5] >> (i0 & 31);
+            const uint32_t l = MODE == 5 ? pay[Pw + (i0 >> 5)] >> (i0 & 31) : 0u;
+            // take(centroids, bin) (AS:383) from the planes' bits as they stand: the tables are (-c reversed, c)
+            // (AS:309), so the centroid is a magnitude with plane H's bit as its sign (set: positive) -- the one
+            // magnitude at 1 bit; at 2 bits the inner one in bins 1 and 2, where the two planes differ.  Four bit
+            // operations per coordinate, where building the bin and eden_cent's masks over it take thirteen, in a
+            // pass bound by its VALU count.
+            const uint32_t neg = ~h, inner = h ^ l;
+            const uint32_t m1 = __float_as_uint(cs.c1), m2 = __float_as_uint(cs.c2), m3 = __float_as_uint(cs.c3);
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const uint32_t sign = (neg << (31 - i)) & 0x80000000u;
+                const uint32_t in = (uint32_t)((int32_t)(inner << (31 - i)) >> 31);       // all ones: the inner magnitude
+                const uint32_t mag = MODE == 4 ? m1 : (in & m2) | (~in & m3);
+                v[i] = __uint_as_float((mag & 0x7FFFFFFFu) | sign);
+            }
         } else {
             const float* p = (const float*)a.in + vec * D + i0;
 #pragma unroll
@@ -547,6 +568,13 @@ template <bool LAST, bool RECV_LAST>
 __global__ void __launch_bounds__(256)
 fwht_low4096_frac_kernel(FwhtArgs a, EdenMask mask) {
     fwht_low4096_body<3, LAST, RECV_LAST>(a, mask);
+}
+// the receiver's first pass on a bit-packed message (uq_eden_decompress_packed_f32): MODE 4 (1 bit) or 5 (2 bits)
+template <int MODE, bool LAST, bool RECV_LAST>
+__global__ void __launch_bounds__(256)
+fwht_low4096_packed_kernel(FwhtArgs a) {
+    static_assert(MODE == 4 || MODE == 5, "the packed forms of the receiver's first pass");
+    fwht_low4096_body<MODE, LAST, RECV_LAST>(a, EdenMask{});
 }
 
 // First pass over 16384 contiguous elements (bits 0-13), for D = 2^22: 14 + 8 bits instead of
@@ -1468,16 +1496,50 @@ __device__ __forceinline__ float eden_thresh(float b, float nv) {
 // AS:352-368.  A step's 64 coordinates are two mask words, so a register set of U steps holds its
 // 2 U words one per lane (MA / MB); a step reads its two by lane index into a scalar pair, which
 // is the step's lane predicate as it stands (no shift or test per lane).
-template <int NB, bool THR, bool FRAC = false>
+template <int K, int N, class F>
+__device__ __forceinline__ void static_for(F&& f) {                       // f(integral_constant<K>) ... f(<N - 1>)
+    if constexpr (K < N) {
+        f(std::integral_constant<int, K>{});
+        static_for<K + 1, N>(f);
+    }
+}
+// Lanes L and L + 1 of w = the halves of a wave-uniform 64-bit value (v_writelane_b32; the lane is an inline
+// constant, so the value may sit in any SGPR pair).  The value is a ballot, i.e. an SGPR pair a v_cmp may have just
+// written: gfx940 and later need 2 wait states between a VALU write of an SGPR and a VALU read of it (the
+// compiler's own `s_nop 1` between a v_cmp and the v_cndmask that reads its mask), and inline asm is not scanned
+// for it -- a v_writelane right behind its v_cmp wrote the pair's previous content.  Hence the s_nop 1.
+template <int L>
+__device__ __forceinline__ void write_lanes(int& w, uint64_t b) {
+    asm volatile("s_nop 1\n\tv_writelane_b32 %0, %1, %3\n\tv_writelane_b32 %0, %2, %4"
+                 : "+v"(w)
+                 : "s"((uint32_t)b), "s"((uint32_t)(b >> 32)), "n"(L), "n"(L + 1));
+}
+// ... of two words from two values, behind one s_nop
+template <int L>
+__device__ __forceinline__ void write_lanes(int& w, uint64_t b, int& w2, uint64_t b2) {
+    asm volatile("s_nop 1\n\tv_writelane_b32 %0, %2, %6\n\tv_writelane_b32 %0, %3, %7\n\t"
+                 "v_writelane_b32 %1, %4, %6\n\tv_writelane_b32 %1, %5, %7"
+                 : "+v"(w), "+v"(w2)
+                 : "s"((uint32_t)b), "s"((uint32_t)(b >> 32)), "s"((uint32_t)b2), "s"((uint32_t)(b2 >> 32)), "n"(L), "n"(L + 1));
+}
+
+// PK (1 and 2 bits): the bins go out bit-packed (plane H, the bin's high bit, in words [0, D / 32) of
+// the client's payload row `bj`, plane L after it at 2 bits): a step's 64 bins are one wave ballot per plane, a
+// register set's ballots are gathered one word per lane (v_writelane) and stored as one dword per lane.  D is a
+// power of two (the padded length), so a tail below 64 coordinates is the row's only word.
+template <int NB, bool THR, bool FRAC = false, bool PK = false>
 __device__ __forceinline__ float dotbins_chains(const float* __restrict__ vj, int64_t D, float sqrtD, float nv,
                                                 const EdenTables& tab, const EdenCents& cs, const float (&T)[NB],
                                                 uint8_t* __restrict__ bj, int lane,
                                                 const uint32_t* __restrict__ mrow = nullptr, float lo0 = 0.f,
                                                 float lo1 = 0.f) {
     static_assert(!FRAC || NB == 3, "the fractional rates mix the 1-bit table into the 2-bit one");
+    static_assert(!PK || !FRAC, "the fractional rates are packed by the converter");
     const __amdgpu_buffer_rsrc_t rv = make_rsrc(vj, (uint32_t)(D * 4));
-    const __amdgpu_buffer_rsrc_t rb = make_rsrc(bj, (uint32_t)D);
+    const uint32_t Pw = (uint32_t)((D + 31) / 32);                         // PK: words of a plane
+    const __amdgpu_buffer_rsrc_t rb = make_rsrc(bj, PK ? Pw * (NB == 1 ? 4u : 8u) : (uint32_t)D);
     float acc = 0.f;
+    bool lasth = false, lastl = false;                                     // PK: the bits of the bin of the lane's last step
     auto step = [&](float x, int64_t i, bool hi = false) {                 // bins[i], acc = fma(c[bin], x, acc)
         const float y = x * sqrtD;                                          // AS:329 vec * sqrt(D)
         int b;
@@ -1497,6 +1559,19 @@ __device__ __forceinline__ float dotbins_chains(const float* __restrict__ vj, in
             acc = fmaf(eden_cent_mixed(cs, lo0, lo1, b, hs), x, acc);       // AS:364-366
             return;
         }
+        if constexpr (PK && THR && NB == 3) {
+            // The packed form needs the bin's two bits as lane masks, not the bin: T[0] <= T[1] <= T[2] (eden_thresh is
+            // monotone in the boundary), so the high bit is the middle compare and the low bit the parity of the three
+            // (NaN: all three, bin 3), and the centroid (AS:335) is a magnitude -- the inner one in bins 1 and 2, i.e.
+            // above T[0] and not above T[2] -- with the middle compare's sign: the table is (-c reversed, c), AS:309.
+            // Two selects where the bin, its tests and eden_cent's masks take seventeen VALU instructions.
+            const bool c0 = !(y <= T[0]), c1 = !(y <= T[1 % NB]), c2 = !(y <= T[2 % NB]);
+            lasth = c1;
+            lastl = (c0 != c1) != c2;
+            const float mag = (c0 && !c2) ? cs.c2 : cs.c3;
+            acc = fmaf(c1 ? mag : -mag, x, acc);
+            return;
+        }
         if (THR) {
             b = !(y <= T[0]) ? 1 : 0;
 #pragma unroll
@@ -1504,9 +1579,16 @@ __device__ __forceinline__ float dotbins_chains(const float* __restrict__ vj, in
         } else {
             b = eden_bin(tab, y / nv);
         }
-        __builtin_amdgcn_raw_buffer_store_b8((uint8_t)b, rb, (uint32_t)i, 0, 0);
+        if constexpr (PK) {
+            lasth = NB == 1 ? b != 0 : b >= 2;
+            lastl = (b & 1) != 0;
+        } else {
+            __builtin_amdgcn_raw_buffer_store_b8((uint8_t)b, rb, (uint32_t)i, 0, 0);
+        }
         acc = fmaf(eden_cent(cs, b), x, acc);                               // AS:335
     };
+    auto ballot_h = [&]() { return __builtin_amdgcn_ballot_w64(lasth); };
+    auto ballot_l = [&]() { return __builtin_amdgcn_ballot_w64(lastl); };
     const int64_t steps = D / 64;
     auto pipelined = [&](auto u) {                                         // u steps per register set
         constexpr int U = decltype(u)::value;
@@ -1531,12 +1613,33 @@ __device__ __forceinline__ float dotbins_chains(const float* __restrict__ vj, in
                 }
             }
         };
+        // PK: the set's 2 U words of plane H (and L), word 2 s0 + l in lane l: step k's ballot halves go to lanes
+        // 2 k and 2 k + 1, then one dword store per lane
+        auto run_pk = [&](const float (&R)[U], int64_t s0) {
+            int wh = 0, wl = 0;
+            static_for<0, U>([&](auto kk) {
+                constexpr int k = decltype(kk)::value;
+                step(R[k], (s0 + k) * 64 + lane);
+                if (NB > 1) write_lanes<2 * k>(wh, ballot_h(), wl, ballot_l());
+                else write_lanes<2 * k>(wh, ballot_h());
+                // a step's lane masks die here: without the fence the scheduler interleaves a set's steps and
+                // keeps their masks alive side by side (344 SGPR spills at 2 bits)
+                if (NB > 1) __builtin_amdgcn_sched_barrier(0);
+            });
+            if (2 * U == 64 || lane < 2 * U) {                             // (past the row: the buffer drops it)
+                const uint32_t w = (uint32_t)(2 * s0 + lane);
+                __builtin_amdgcn_raw_buffer_store_b32((uint32_t)wh, rb, w * 4u, 0, 0);
+                if (NB > 1) __builtin_amdgcn_raw_buffer_store_b32((uint32_t)wl, rb, (Pw + w) * 4u, 0, 0);
+            }
+        };
         load(A, MA, 0);
         for (int64_t s0 = 0; s0 < steps; s0 += 2 * U) {
             load(B, MB, s0 + U);
-            run(A, MA, s0);
+            if constexpr (PK) run_pk(A, s0);
+            else run(A, MA, s0);
             load(A, MA, s0 + 2 * U);
-            run(B, MB, s0 + U);
+            if constexpr (PK) run_pk(B, s0 + U);
+            else run(B, MB, s0 + U);
         }
     };
     if (steps >= 2 * kDotU && steps % (2 * kDotU) == 0) {
@@ -1551,8 +1654,22 @@ __device__ __forceinline__ float dotbins_chains(const float* __restrict__ vj, in
         if (FRAC) step(vj[i], i, mask_bit(mrow, i) != 0u);
         else step(vj[i], i);
     };
+    // PK: the words of coordinates [c0, c0 + 64) from the lanes' last bins (0 in a lane that had no coordinate)
+    auto flush = [&](int64_t c0) {
+        const uint64_t h = ballot_h(), l = ballot_l();
+        const uint32_t w = (uint32_t)(c0 >> 5) + (uint32_t)lane;
+        if (lane < 2 && c0 + 32 * lane < D) {
+            __builtin_amdgcn_raw_buffer_store_b32(lane ? (uint32_t)(h >> 32) : (uint32_t)h, rb, w * 4u, 0, 0);
+            if (NB > 1) __builtin_amdgcn_raw_buffer_store_b32(lane ? (uint32_t)(l >> 32) : (uint32_t)l, rb, (Pw + w) * 4u, 0, 0);
+        }
+        lasth = lastl = false;
+    };
     int64_t i0 = 0;
-    for (; i0 + 64 <= D; i0 += 64) at(i0 + lane);
+    for (; i0 + 64 <= D; i0 += 64) {
+        at(i0 + lane);
+        if constexpr (PK) flush(i0);
+    }
+    const int64_t r0 = i0;
     if (D - i0 >= 32) {                                                    // remainder: acc 0 and 1
         if (lane < 32) at(i0 + lane);
         i0 += 32;
@@ -1562,10 +1679,12 @@ __device__ __forceinline__ float dotbins_chains(const float* __restrict__ vj, in
             if (i0 + lane < D) at(i0 + lane);
             else acc = fmaf(0.f, 0.f, acc);
         }
+    if constexpr (PK)
+        if (r0 < D) flush(r0);
     return acc;
 }
 
-template <int NB, bool FRAC>       // boundaries: 1 (1 bit) or 3 (2 bits, and the fractional rates)
+template <int NB, bool FRAC, bool PK = false>       // boundaries: 1 (1 bit) or 3 (2 bits, and the fractional rates)
 __device__ __forceinline__ void
 dotbins_body(const float* __restrict__ v, int64_t D, float sqrtD, const float* __restrict__ nrm, const EdenTables& tab,
              uint8_t* __restrict__ bins, float* __restrict__ scale, int64_t n, const int32_t* __restrict__ redo,
@@ -1589,6 +1708,10 @@ dotbins_body(const float* __restrict__ v, int64_t D, float sqrtD, const float* _
         const uint32_t* mrow = mask_row_of(mask, j, D);
         acc = thr ? dotbins_chains<NB, true, FRAC>(v + j * D, D, sqrtD, nv, tab, cs, T, bins + j * D, lane, mrow, mask.lo0, mask.lo1)
                   : dotbins_chains<NB, false, FRAC>(v + j * D, D, sqrtD, nv, tab, cs, T, bins + j * D, lane, mrow, mask.lo0, mask.lo1);
+    } else if constexpr (PK) {             // `bins`: the payload rows, (D + 31) / 32 words per plane
+        uint8_t* pj = bins + j * ((D + 31) / 32) * (NB == 1 ? 4 : 8);
+        acc = thr ? dotbins_chains<NB, true, false, true>(v + j * D, D, sqrtD, nv, tab, cs, T, pj, lane)
+                  : dotbins_chains<NB, false, false, true>(v + j * D, D, sqrtD, nv, tab, cs, T, pj, lane);
     } else {
         acc = thr ? dotbins_chains<NB, true>(v + j * D, D, sqrtD, nv, tab, cs, T, bins + j * D, lane)
                   : dotbins_chains<NB, false>(v + j * D, D, sqrtD, nv, tab, cs, T, bins + j * D, lane);
@@ -1614,6 +1737,15 @@ __global__ void __launch_bounds__(64 * kDotWaves)
 eden_dotbins_kernel(const float* __restrict__ v, int64_t D, float sqrtD, const float* __restrict__ nrm, EdenTables tab,
                     uint8_t* __restrict__ bins, float* __restrict__ scale, int64_t n, const int32_t* __restrict__ redo) {
     dotbins_body<NB, false>(v, D, sqrtD, nrm, tab, bins, scale, n, redo, EdenMask{});
+}
+
+// KE4 writing bit-packed payload rows (uq_eden_compress_packed_f32): the same chains, so the same scale
+template <int NB>
+__global__ void __launch_bounds__(64 * kDotWaves)
+eden_dotbins_packed_kernel(const float* __restrict__ v, int64_t D, float sqrtD, const float* __restrict__ nrm, EdenTables tab,
+                           uint32_t* __restrict__ payload, float* __restrict__ scale, int64_t n,
+                           const int32_t* __restrict__ redo) {
+    dotbins_body<NB, false, true>(v, D, sqrtD, nrm, tab, reinterpret_cast<uint8_t*>(payload), scale, n, redo, EdenMask{});
 }
 
 // KE4 of the fractional rates (AS:352-368): the 2-bit tables, the table per coordinate by the mask row
@@ -2005,6 +2137,309 @@ eden_normdot1_kernel(const float* __restrict__ v, int64_t n, int64_t D, float sq
         const float mp = __uint_as_float(minpos[ck]);
         const bool ok = nv > 0.f && nv < INFINITY && (mp == INFINITY || mp / nv > 0.f);
         redo[vec] = ok ? 0 : 1;
+    }
+}
+
+// KE2+4 writing bit-packed payload rows (uq_eden_compress_packed_f32; 1 bit: D / 32 words per client): a loader
+// stages its 4 sign-rule bins as one byte (a nibble) instead of four, and a chunk's 2048 bins leave as 64 words per
+// client, one per loader lane, squeezed from the lane's 8 staged bytes -- one 256-byte store per wave and chunk
+// where the u8 form issues two of 1 KB, at the same place after the next loads.
+// EDIT TOGETHER with eden_normdot1_kernel above: the same text but for the staging and the store of the bins (a
+// shared body moved the u8 kernel's instructions; tools/kernel_table.py compares the two builds).
+__global__ void __launch_bounds__(kNDThreads)
+eden_normdot1_packed_kernel(const float* __restrict__ v, int64_t n, int64_t D, float sqrtD, EdenTables tab,
+                            float* __restrict__ nrm, uint32_t* __restrict__ payload, float* __restrict__ scale,
+                            int32_t* __restrict__ redo) {
+    __shared__ __attribute__((aligned(16))) float s[3][kNormBuf];
+    __shared__ float dacc[kNormClients][64];
+    __shared__ uint32_t minpos[kNormClients];
+    const int tid = threadIdx.x;
+    const int64_t v0 = (int64_t)blockIdx.x * kNormClients;
+    const int64_t nchunks = D / kNormChunk;
+    const bool chain = tid < kWave;
+    const bool loader = tid >= kWave && tid < kWave + 256;
+    const bool dotw = tid >= kWave + 256;
+    const int lt = tid - kWave, lk = lt >> 6, lj = lt & 63;
+    const bool lvalid = loader && v0 + lk < n;
+    const float* lp = v + (lvalid ? v0 + lk : 0) * D;
+    uint32_t* lb = payload + (lvalid ? v0 + lk : 0) * (D / 32);
+    if (tid < kNormClients) minpos[tid] = 0x7F800000u;                 // +inf
+    constexpr int kLQ = kNormChunk / 256;
+    float4 na[kLQ], nb[kLQ];
+    uint32_t mymin = 0x7F800000u;                                      // bits of the smallest positive y
+    auto load = [&](float4 (&nx)[kLQ], int64_t ch) {
+        if (!lvalid || ch >= nchunks) return;
+#pragma unroll
+        for (int q = 0; q < kLQ; ++q) nx[q] = ld_stream(reinterpret_cast<const float4*>(lp + ch * kNormChunk + 4 * (lj + 64 * q)));
+    };
+    // The bins of a chunk are computed when it is staged, kept in LDS (sbins, two chunks: a byte per 4
+    // coordinates), and written after the next barrier by the loaders as one word per lane, issued after
+    // the next loads (the u8 kernel's note on vmcnt's order).
+    __shared__ __attribute__((aligned(16))) uint8_t sbins[2][kNormClients][kNormChunk / 4];
+    auto store = [&](const float4 (&nx)[kLQ], float* sb, int64_t ch) {
+        if (!loader) return;
+#pragma unroll
+        for (int q = 0; q < kLQ; ++q) {
+            const int e = 4 * (lj + 64 * q);
+            const int i = e >> 3, l = e & 7;
+            float* base = sb + lk * kNormClientStride + i;
+            base[(l + 0) * kNormRow] = nx[q].x;
+            base[(l + 1) * kNormRow] = nx[q].y;
+            base[(l + 2) * kNormRow] = nx[q].z;
+            base[(l + 3) * kNormRow] = nx[q].w;
+            const float xs[4] = {nx[q].x, nx[q].y, nx[q].z, nx[q].w};   // the bins of these 4 (sign rule)
+            uint32_t w = 0;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const float y = xs[c] * sqrtD;
+                w |= (!(y <= 0.f) ? 1u : 0u) << c;
+                if (lvalid && y > 0.f) mymin = min(mymin, __float_as_uint(y));
+            }
+            sbins[ch & 1][lk][lj + 64 * q] = (uint8_t)w;
+        }
+    };
+    auto flush_bins = [&](int64_t ch) {          // chunk ch's bins, staged before the last barrier
+        if (!lvalid) return;
+        // word lj of the chunk: coordinates 32 lj .. 32 lj + 31, the nibbles of staged bytes 8 lj .. 8 lj + 7
+        const u32x2v t = *reinterpret_cast<const u32x2v*>(&sbins[ch & 1][lk][8 * lj]);
+        auto squeeze = [](uint32_t a) {          // nibbles at bits 0, 8, 16, 24 -> bits 0..15
+            a = (a | (a >> 4)) & 0x00FF00FFu;
+            return (a | (a >> 8)) & 0xFFFFu;
+        };
+        __builtin_nontemporal_store(squeeze(t.x) | (squeeze(t.y) << 16), lb + ch * (kNormChunk / 32) + lj);
+    };
+    const int ck = (tid >> 3) & (kNormClients - 1), cl = tid & 7;
+    float acc = 0.f;
+    const int dk = (tid - kWave - 256) >> 6, dl = tid & 63;           // dot wave: client dk, chain dl
+    const EdenCents cs = eden_cents(tab);
+    auto chainstep = [&](int64_t ch) {
+        if (chain) {
+            const float* row = s[ch % 3] + ck * kNormClientStride + cl * kNormRow;
+            for (int i = 0; i < kNormChunk / 8; i += 16) {
+                float4 t[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) t[u] = *reinterpret_cast<const float4*>(row + i + 4 * u);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    acc = fmaf(t[u].x, t[u].x, acc);
+                    acc = fmaf(t[u].y, t[u].y, acc);
+                    acc = fmaf(t[u].z, t[u].z, acc);
+                    acc = fmaf(t[u].w, t[u].w, acc);
+                }
+            }
+        } else if (dotw) {
+            // element 64 s + dl of the chunk sits at lane (dl % 8), step 8 s + dl / 8 of the image
+            const float* row = s[ch % 3] + dk * kNormClientStride + (dl & 7) * kNormRow + (dl >> 3);
+#pragma unroll 8
+            for (int st = 0; st < kNormChunk / 64; ++st) {
+                const float x = row[8 * st];
+                const float c = !(x * sqrtD <= 0.f) ? cs.c1 : cs.c0;   // AS:335 take(centroids, bins)
+                acc = fmaf(c, x, acc);
+            }
+        }
+    };
+    if (loader) {
+        load(na, 0);
+        store(na, s[0], 0);
+        load(na, 1);
+        load(nb, 2);
+    }
+    __syncthreads();
+    for (int64_t ch = 0; ch < nchunks; ch += 2) {
+        chainstep(ch);
+        if (loader && ch + 1 < nchunks) {
+            store(na, s[(ch + 1) % 3], ch + 1);
+            load(na, ch + 3);
+        }
+        if (loader) flush_bins(ch);
+        __syncthreads();
+        if (ch + 1 >= nchunks) break;
+        chainstep(ch + 1);
+        if (loader && ch + 2 < nchunks) {
+            store(nb, s[(ch + 2) % 3], ch + 2);
+            load(nb, ch + 4);
+        }
+        if (loader) flush_bins(ch + 1);
+        __syncthreads();
+    }
+    if (lvalid) atomicMin(&minpos[lk], mymin);
+    if (dotw) dacc[dk][dl] = acc;
+    float nv = 0.f;
+    if (chain) {
+        const int base = tid & ~7;
+        float tot = __shfl(acc, base, kWave);
+        for (int j = 1; j < 8; ++j) tot = tot + __shfl(acc, base + j, kWave);
+        nv = sqrtf(tot);
+        const int64_t vec = v0 + ck;
+        if (tid < 8 * kNormClients && cl == 0 && vec < n) nrm[vec] = nv;
+    }
+    __syncthreads();
+    if (chain && tid < 8 * kNormClients && cl == 0 && v0 + ck < n) {
+        const int64_t vec = v0 + ck;
+        const float* a = dacc[ck];
+        float w[16];
+#pragma unroll
+        for (int l = 0; l < 16; ++l) w[l] = (a[l] + a[16 + l]) + (a[32 + l] + a[48 + l]);
+#pragma unroll
+        for (int l = 0; l < 8; ++l) w[l] = w[l] + w[l + 8];
+#pragma unroll
+        for (int l = 0; l < 4; ++l) w[l] = w[l] + w[l + 4];
+        const float dot = (w[0] + w[1]) + (w[2] + w[3]);
+        scale[vec] = (nv * nv) / dot;                                  // AS:335 norm ** 2 / dot
+        const float mp = __uint_as_float(minpos[ck]);
+        const bool ok = nv > 0.f && nv < INFINITY && (mp == INFINITY || mp / nv > 0.f);
+        redo[vec] = ok ? 0 : 1;
+    }
+}
+
+// ---- the bit-packed message form: converters between u8 bins and payload rows --
+// A client's payload is a row of u32 words, coordinate i at bit i % 32 of word i / 32 of a plane (the layout of
+// rht_sign_bits_kernel / eden_mask_bits_kernel), P = ceil(D / 32) words per plane.  Plane H, words [0, P): the
+// bin at 1 bit, bin >> 1 at 2 bits, and at a fractional rate bin >> 1 where the client's mask bit is set and the
+// 1-bit bin where it is clear -- "above the middle boundary" at every rate.  Plane L: none at 1 bit; words
+// [P, 2 P) hold bin & 1 at 2 bits; at a fractional rate the low bits of the mask-set coordinates only, compacted
+// in index order (the r-th set bit of the mask row at bit r % 32 of word P + r / 32).  Every bit that names no
+// coordinate is 0.  KIND: 1, 2, or 3 for the fractional rates.  These replace nothing of the reference, which
+// keeps a message's bins as an int64 tensor (AS:335-350).
+
+// KE0r: the exclusive rank of each mask word, ranks [rows][P + 1] (the last entry: cnt = popcount(row[:D]))
+__global__ void __launch_bounds__(256)
+eden_mask_ranks_kernel(const uint32_t* __restrict__ bits, int64_t D, uint32_t* __restrict__ ranks) {
+    __shared__ uint32_t s[256];
+    const int tid = threadIdx.x;
+    const int64_t W = (D + 31) / 32;
+    const uint32_t* row = bits + (int64_t)blockIdx.x * W;
+    uint32_t* out = ranks + (int64_t)blockIdx.x * (W + 1);
+    uint32_t carry = 0;
+    for (int64_t base = 0; base < W; base += 256) {
+        const int64_t w = base + tid;
+        uint32_t c = 0;
+        if (w < W) {
+            const uint32_t m = row[w];
+            c = (uint32_t)__popc(D - 32 * w >= 32 ? m : m & ((1u << (D - 32 * w)) - 1u));
+        }
+        s[tid] = c;
+        __syncthreads();
+        for (int off = 1; off < 256; off <<= 1) {
+            const uint32_t t = tid >= off ? s[tid - off] : 0u;
+            __syncthreads();
+            s[tid] += t;
+            __syncthreads();
+        }
+        if (w < W) out[w] = carry + s[tid] - c;
+        carry += s[255];
+        __syncthreads();
+    }
+    if (tid == 0) out[W] = carry;
+}
+
+struct PackRows {
+    const uint32_t* mask;     // [rows][P] (KIND 3)
+    const uint32_t* ranks;    // [rows][P + 1]
+    const int32_t* row;       // [n] or null: row 0
+};
+__device__ __forceinline__ uint32_t mask_word(const uint32_t* __restrict__ mrow, int64_t w, int64_t D) {
+    const uint32_t m = mrow[w];
+    return D - 32 * w >= 32 ? m : m & ((1u << (D - 32 * w)) - 1u);
+}
+
+// payload_bits[j] = D, 2 D or D + cnt_j
+__global__ void __launch_bounds__(256)
+eden_payload_bits_kernel(int64_t n, int64_t D, int kind, PackRows r, int64_t* __restrict__ payload_bits) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    const int64_t P = (D + 31) / 32;
+    payload_bits[j] = kind == 1 ? D : kind == 2 ? 2 * D : D + (int64_t)r.ranks[(int64_t)(r.row ? r.row[j] : 0) * (P + 1) + P];
+}
+
+// One thread per payload word (grid.y: the client).
+template <int KIND>
+__global__ void __launch_bounds__(256)
+eden_pack_bins_kernel(const uint8_t* __restrict__ bins, int64_t D, PackRows r, uint32_t* __restrict__ payload) {
+    const int64_t P = (D + 31) / 32, pitch = KIND == 1 ? P : 2 * P;
+    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x, j = blockIdx.y;
+    if (q >= pitch) return;
+    const uint8_t* b = bins + j * D;
+    const int64_t mr = KIND == 3 && r.row ? r.row[j] : 0;
+    const uint32_t* mrow = KIND == 3 ? r.mask + mr * P : nullptr;
+    uint32_t w = 0;
+    if (q < P || KIND == 2) {                                              // a plane in index order
+        const int64_t wq = q < P ? q : q - P, i0 = 32 * wq;
+        const int cnt = (int)min((int64_t)32, D - i0);
+        const uint32_t m = KIND == 3 ? mask_word(mrow, wq, D) : KIND == 2 && q < P ? ~0u : 0u;   // bits that take bin >> 1
+        uint32_t lo = 0, hi = 0;
+        if (cnt == 32 && (((uintptr_t)(b + i0)) & 15) == 0) {
+            const uint4 t[2] = {*reinterpret_cast<const uint4*>(b + i0), *reinterpret_cast<const uint4*>(b + i0 + 16)};
+            const uint8_t* tb = reinterpret_cast<const uint8_t*>(t);
+#pragma unroll
+            for (int k = 0; k < 32; ++k) { lo |= (uint32_t)(tb[k] & 1u) << k; hi |= (uint32_t)((tb[k] >> 1) & 1u) << k; }
+        } else {
+            for (int k = 0; k < cnt; ++k) { lo |= (uint32_t)(b[i0 + k] & 1u) << k; hi |= (uint32_t)((b[i0 + k] >> 1) & 1u) << k; }
+        }
+        w = (hi & m) | (lo & ~m);
+    } else if (KIND == 3) {                                                // plane L of a fractional rate: ranks [32 wq, 32 wq + 32)
+        const uint32_t* rk = r.ranks + mr * (P + 1);
+        const uint32_t r0 = (uint32_t)(32 * (q - P));
+        if (r0 < rk[P]) {
+            int64_t lo = 0, hi = P;                                        // rk[lo] <= r0 < rk[hi]
+            while (hi - lo > 1) {
+                const int64_t mid = lo + ((hi - lo) >> 1);
+                if (rk[mid] <= r0) lo = mid;
+                else hi = mid;
+            }
+            uint32_t skip = r0 - rk[lo];
+            int filled = 0;
+            for (int64_t mw = lo; mw < P && filled < 32; ++mw) {
+                uint32_t m = mask_word(mrow, mw, D);
+                while (m && filled < 32) {
+                    const int k = __ffs((int)m) - 1;
+                    m &= m - 1u;
+                    if (skip) { --skip; continue; }
+                    w |= (uint32_t)(b[32 * mw + k] & 1u) << filled;
+                    ++filled;
+                }
+            }
+        }
+    }
+    payload[j * pitch + q] = w;
+}
+
+// One thread per 32 coordinates: the u8 bins uq_eden_compress_f32 / _frac_f32 write (0..3 where the table is the
+// 2-bit one, 0..1 elsewhere)
+template <int KIND>
+__global__ void __launch_bounds__(256)
+eden_unpack_bins_kernel(const uint32_t* __restrict__ payload, int64_t D, PackRows r, uint8_t* __restrict__ bins) {
+    const int64_t P = (D + 31) / 32, pitch = KIND == 1 ? P : 2 * P;
+    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x, j = blockIdx.y;
+    if (q >= P) return;
+    const uint32_t* pay = payload + j * pitch;
+    const int64_t i0 = 32 * q;
+    const int cnt = (int)min((int64_t)32, D - i0);
+    const uint32_t h = pay[q];
+    uint32_t m = 0, l = 0;                                                 // the coordinates with a low bit, and those bits in place
+    if (KIND == 2) { m = ~0u; l = pay[P + q]; }
+    if (KIND == 3) {
+        const int64_t mr = r.row ? r.row[j] : 0;
+        m = mask_word(r.mask + mr * P, q, D);
+        uint32_t rk = r.ranks[mr * (P + 1) + q];
+        for (uint32_t t = m; t; t &= t - 1u, ++rk)
+            if ((rk >> 5) < P)                                             // (rank rows of another mask: no read past the row)
+                l |= ((pay[P + (rk >> 5)] >> (rk & 31)) & 1u) << (__ffs((int)t) - 1);
+    }
+    uint32_t o[8];
+#pragma unroll
+    for (int k = 0; k < 32; ++k) {
+        const uint32_t hb = (h >> k) & 1u, mb = (m >> k) & 1u;
+        const uint32_t bin = mb ? (hb << 1) | ((l >> k) & 1u) : hb;
+        if (k % 4 == 0) o[k / 4] = 0;
+        o[k / 4] |= bin << (8 * (k % 4));
+    }
+    uint8_t* b = bins + j * D + i0;
+    if (cnt == 32 && (((uintptr_t)b) & 15) == 0) {
+        *reinterpret_cast<uint4*>(b) = make_uint4(o[0], o[1], o[2], o[3]);
+        *reinterpret_cast<uint4*>(b + 16) = make_uint4(o[4], o[5], o[6], o[7]);
+    } else {
+        for (int k = 0; k < cnt; ++k) b[k] = (uint8_t)(o[k / 4] >> (8 * (k % 4)));
     }
 }
 

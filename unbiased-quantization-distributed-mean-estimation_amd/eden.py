@@ -32,7 +32,8 @@ import torch
 from . import _lib, _runtime
 from ._runtime import as_batch_f32, as_vector_f32, ptr, stream_ptr, workspace_for
 
-__all__ = ["EDEN_quantize_Hadamard", "eden_quantize", "eden_compress", "eden_decompress", "EdenMessage", "eden_mask_bits",
+__all__ = ["EDEN_quantize_Hadamard", "eden_quantize", "eden_compress", "eden_decompress", "eden_pack", "eden_unpack",
+           "EdenMessage", "eden_mask_bits", "eden_mask_ranks", "packed_words",
            "rht_signs", "padded_dim", "randomized_hadamard_transform", "randomized_inverse_hadamard_transform"]
 
 _SEEDS = 100                       # AS:797 torch.randint(0, 100)
@@ -231,6 +232,7 @@ class _MaskCache(_SignCache):
     def __init__(self, budget_bytes: int = 1 << 30):
         super().__init__(budget_bytes)
         self.builds = 0
+        self.rank_builds = 0           # rank rows built (uq_eden_mask_ranks: the packed form of these rates)
 
 
 _masks = _MaskCache()
@@ -250,35 +252,89 @@ def eden_mask_bits(seeds, D: int, threshold: int, device=None) -> torch.Tensor:
     return out
 
 
-def _mask_table(seeds: torch.Tensor, D: int, T: int, dev):
-    """The mask rows in the layout of _sign_rows' table for the same seeds, so that a client's sign
-    row index is its mask row index too: rows of seeds 0..99 when every seed is in that range, the
-    one row of a single other seed, else a row per distinct seed in sorted order."""
+def _mask_key(seeds: torch.Tensor, D: int, T: int, dev):
+    """(cache key, seeds of the table's rows, whether _masks keeps it) of the mask table of these seeds: the
+    layout of _sign_rows' table for the same seeds, so that a client's sign row index is its mask row index
+    too: rows of seeds 0..99 when every seed is in that range, the one row of a single other seed, else a
+    row per distinct seed in sorted order (kept for up to four)."""
     seeds_cpu = seeds.to("cpu", torch.int64).reshape(-1)
     if bool(((seeds_cpu >= 0) & (seeds_cpu < _SEEDS)).all()):
-        key, rows, keep = (dev.index, D, T, "ref"), torch.arange(_SEEDS), True
-    elif seeds_cpu.numel() == 1:
-        key, rows, keep = (dev.index, D, T, "one", int(seeds_cpu[0])), seeds_cpu, True
-    else:
-        rows = torch.unique(seeds_cpu)
-        key, keep = (dev.index, D, T, tuple(rows.tolist())), rows.numel() <= 4
+        return (dev.index, D, T, "ref"), torch.arange(_SEEDS), True
+    if seeds_cpu.numel() == 1:
+        return (dev.index, D, T, "one", int(seeds_cpu[0])), seeds_cpu, True
+    rows = torch.unique(seeds_cpu)
+    return (dev.index, D, T, tuple(rows.tolist())), rows, rows.numel() <= 4
+
+
+def _mask_table(seeds: torch.Tensor, D: int, T: int, dev, ranks: bool = False):
+    """The mask rows of these seeds (_mask_key's layout); ranks=True: (mask rows, their rank rows), the rank
+    rows kept in _masks beside the mask rows, under the same key and within the same byte budget: both are
+    pure functions of the key, so a warm call builds neither."""
+    key, rows, keep = _mask_key(seeds, D, T, dev)
     if not keep:
-        return eden_mask_bits(rows, D, T, dev)
+        tab = eden_mask_bits(rows, D, T, dev)
+        return (tab, eden_mask_ranks(tab, D)) if ranks else tab
     with _cache_lock:
         tab = _masks.get(key)
         if tab is None:
             tab = eden_mask_bits(rows, D, T, dev)
             _masks.put(key, tab)
-        return tab
+        if not ranks:
+            return tab
+        rk = _masks.get(key + ("ranks",))
+        if rk is None:
+            rk = eden_mask_ranks(tab, D)
+            _masks.put(key + ("ranks",), rk)
+        return tab, rk
+
+
+def eden_mask_ranks(mask_bits: torch.Tensor, D: int) -> torch.Tensor:
+    """int32 [rows, ceil(D / 32) + 1]: the set bits before each word of every mask row, and the row's
+    count in its last entry (uq_eden_mask_ranks): where the packed form of a fractional message puts
+    the low bits of the coordinates that have one."""
+    rows = mask_bits.shape[0]
+    out = torch.empty((rows, (D + 31) // 32 + 1), dtype=torch.int32, device=mask_bits.device)
+    _lib.check(_lib.load().uq_eden_mask_ranks(ptr(mask_bits), rows, D, ptr(out), stream_ptr(mask_bits.device)),
+               "uq_eden_mask_ranks")
+    with _count_lock:
+        _masks.rank_builds += 1
+    return out
+
+
+_KIND_FRAC = 12              # UQ_EDEN_NBITS_FRAC
+
+
+def _kind(nb) -> int:
+    return _KIND_FRAC if isinstance(nb, tuple) else nb
+
+
+def packed_words(D: int, nb) -> int:
+    """Words of a client's payload row (uq_eden_packed_words): ceil(D / 32) at 1 bit, twice that else."""
+    P = (D + 31) // 32
+    return P if _kind(nb) == 1 else 2 * P
 
 
 @dataclass
 class EdenMessage:
-    bins: torch.Tensor      # u8 [n, D]
+    bins: torch.Tensor      # u8 [n, D], or None for a packed message
     scale: torch.Tensor     # f32 [n]
     seeds: torch.Tensor     # int64 [n] (rotation seeds)
     nbits: object           # 1, 2, or the reference's (1, 2, p_high) for a fractional rate (AS:390)
     dim: int
+    payload: torch.Tensor = None          # int32 [n, pitch]: the bins bit-packed (include/uq_dme.h has the layout)
+    payload_bits: torch.Tensor = None     # int64 [n]: D, 2 D, or D + the client's mask count
+
+    @property
+    def packed(self) -> bool:
+        return self.bins is None
+
+    @property
+    def nbytes(self) -> int:
+        """Bytes of the bins as this message holds them: ceil(payload_bits / 8) per client when packed,
+        a byte per coordinate else."""
+        if self.bins is None:
+            return int(((self.payload_bits + 7) // 8).sum().item())
+        return int(self.bins.shape[0] * self.bins.shape[1])
 
 
 def _prologue(x, bits_per_dimension, seeds, generator):
@@ -308,26 +364,108 @@ def _call(name, dev, seeds, n, d, D, nb, head, tail):
                                             ptr(ws), ws.numel(), stream_ptr(dev)), fn)
 
 
-def eden_compress(x, bits_per_dimension=1, seeds=None, *, generator=None) -> EdenMessage:
-    """EdenSender.compress (AS:355-376) for every row of x [n, d]."""
+def _mask_rows(seeds, D, nb, dev, rows):
+    """(mask rows, their rank rows, row per client) of a fractional rate for the packed entry points; three
+    nulls at 1 and 2 bits.  The mask row index is the sign row index (_mask_table)."""
+    if not isinstance(nb, tuple):
+        return None, None, None
+    mb, rk = _mask_table(seeds, D, _threshold(nb[2]), dev, ranks=True)
+    return mb, rk, rows
+
+
+def _call_packed(name, dev, seeds, n, d, D, nb, head, tail):
+    """uq_eden_<name>_packed_f32(*head, n, d, kind, signs of D, sign rows, sign bits, mask rows, rank rows,
+    mask row per client, *tail, workspace, stream); nothing to run for an empty batch."""
+    if n and d:
+        tab, rows, sb = _sign_rows_bits(seeds, D, dev)
+        kind = _kind(nb)
+        ws = workspace_for("uq_eden_packed_workspace_bytes", dev, n, d, kind)
+        mb, rk, mr = _mask_rows(seeds, D, nb, dev, rows)
+        fn = f"uq_eden_{name}_packed_f32"
+        _lib.check(getattr(_lib.load(), fn)(*map(ptr, head), n, d, kind, ptr(tab), ptr(rows), ptr(sb), ptr(mb), ptr(rk),
+                                            ptr(mr), *map(ptr, tail), ptr(ws), ws.numel(), stream_ptr(dev)), fn)
+
+
+def eden_compress(x, bits_per_dimension=1, seeds=None, *, generator=None, packed: bool = False) -> EdenMessage:
+    """EdenSender.compress (AS:355-376) for every row of x [n, d].  packed=True: the message at its rate,
+    the bins bit-packed into `payload` rows written by the kernels that compute them (bins is None); the
+    same scale, and eden_unpack gives the u8 bins back."""
     dev, x, nb, s = _prologue(x, bits_per_dimension, seeds, generator)
     n, d = x.shape
-    bins = torch.empty((n, padded_dim(d)), dtype=torch.uint8, device=dev)
+    D = padded_dim(d)
     scale = torch.empty(n, dtype=torch.float32, device=dev)
+    if packed:
+        payload = torch.zeros((n, packed_words(D, nb)), dtype=torch.int32, device=dev) if not d else \
+            torch.empty((n, packed_words(D, nb)), dtype=torch.int32, device=dev)
+        pbits = torch.zeros(n, dtype=torch.int64, device=dev)
+        _call_packed("compress", dev, s, n, d, D, nb, (x,), (payload, pbits, scale))
+        return EdenMessage(bins=None, scale=scale, seeds=s, nbits=nb, dim=d, payload=payload, payload_bits=pbits)
+    bins = torch.empty((n, D), dtype=torch.uint8, device=dev)
     _call("compress_f32", dev, s, n, d, bins.shape[1], nb, (x,), (bins, scale))
     return EdenMessage(bins=bins, scale=scale, seeds=s, nbits=nb, dim=d)
 
 
 def eden_decompress(msg: EdenMessage) -> torch.Tensor:
-    """EdenReceiver.decompress (AS:383-413) for every row."""
+    """EdenReceiver.decompress (AS:383-413) for every row, of a u8 or a packed message: the same bits."""
     dev = _runtime.device()
-    bins = msg.bins.to(dev).contiguous()
     scale = msg.scale.to(device=dev, dtype=torch.float32).contiguous()
-    n = bins.shape[0]
     d = msg.dim
+    if msg.bins is None:
+        payload = msg.payload.to(dev).contiguous()
+        n, D, nb = payload.shape[0], padded_dim(d), _bits(msg.nbits)
+        if payload.shape[1] != packed_words(D, nb) or payload.element_size() != 4:
+            raise ValueError("a packed EDEN message's payload is [n, packed_words(D, nbits)] 32-bit words")
+        out = torch.empty((n, d), dtype=torch.float32, device=dev)
+        _call_packed("decompress", dev, torch.as_tensor(msg.seeds), n, d, D, nb, (payload, scale), (out,))
+        return out
+    bins = msg.bins.to(dev).contiguous()
+    n = bins.shape[0]
     out = torch.empty((n, d), dtype=torch.float32, device=dev)
     _call("decompress_f32", dev, torch.as_tensor(msg.seeds), n, d, bins.shape[1], _bits(msg.nbits), (bins, scale), (out,))
     return out
+
+
+def _convert(fn, dev, msg, n, D, nb, src, dst, extra=()):
+    """uq_eden_pack_bins / uq_eden_unpack_bins on the message's rows (the mask and rank rows of its seeds at a
+    fractional rate)."""
+    if n and D:
+        seeds = torch.as_tensor(msg.seeds)
+        rows = _sign_rows(seeds, D, dev)[1] if isinstance(nb, tuple) else None
+        mb, rk, mr = _mask_rows(seeds, D, nb, dev, rows)
+        _lib.check(getattr(_lib.load(), fn)(ptr(src), n, D, _kind(nb), ptr(mb), ptr(rk), ptr(mr), ptr(dst), *map(ptr, extra),
+                                            stream_ptr(dev)), fn)
+
+
+def eden_pack(msg: EdenMessage) -> EdenMessage:
+    """The packed form of a u8 message (uq_eden_pack_bins, on the GPU): what eden_compress(..., packed=True)
+    returns for the same input.  A packed message comes back as it is."""
+    if msg.bins is None:
+        return msg
+    dev = _runtime.device()
+    nb = _bits(msg.nbits)
+    bins = msg.bins.to(dev).contiguous()
+    n, D = bins.shape
+    payload = torch.zeros((n, packed_words(D, nb)), dtype=torch.int32, device=dev)
+    pbits = torch.zeros(n, dtype=torch.int64, device=dev)
+    _convert("uq_eden_pack_bins", dev, msg, n, D, nb, bins, payload, (pbits,))
+    return EdenMessage(bins=None, scale=msg.scale, seeds=msg.seeds, nbits=msg.nbits, dim=msg.dim, payload=payload,
+                       payload_bits=pbits)
+
+
+def eden_unpack(msg: EdenMessage) -> EdenMessage:
+    """The u8 form of a packed message (uq_eden_unpack_bins, on the GPU): bins [n, D] as eden_compress writes
+    them.  A u8 message comes back as it is."""
+    if msg.bins is not None:
+        return msg
+    dev = _runtime.device()
+    nb = _bits(msg.nbits)
+    payload = msg.payload.to(dev).contiguous()
+    n, D = payload.shape[0], padded_dim(msg.dim)
+    if payload.shape[1] != packed_words(D, nb) or payload.element_size() != 4:
+        raise ValueError("a packed EDEN message's payload is [n, packed_words(D, nbits)] 32-bit words")
+    bins = torch.zeros((n, D), dtype=torch.uint8, device=dev)
+    _convert("uq_eden_unpack_bins", dev, msg, n, D, nb, payload, bins)
+    return EdenMessage(bins=bins, scale=msg.scale, seeds=msg.seeds, nbits=msg.nbits, dim=msg.dim)
 
 
 def eden_quantize(x, bits_per_dimension=1, seeds=None, *, return_scale: bool = False, generator=None):
