@@ -575,6 +575,54 @@ int uq_quicfl_quantize_f32(const float* x, int64_t n, int64_t dim, const int8_t*
                            float delta, const float* recv_table, int32_t recv_numel, const int32_t* prng_seeds,
                            const uint32_t* px_state, const int32_t* px_seeds, uint32_t* px_state_out, float* out,
                            float* scale, int32_t* info, void* ws, size_t ws_bytes, void* stream);
+/* QUIC-FL messages at their rate: X bit-packed, the exact coordinates as an index list.  These entry points
+ * replace nothing of the reference, whose message dict keeps X and a mask (AS:494-503).  D: the padded
+ * power-of-two dimension (<= 2^28), nbits 1..4, P = ceil(D / 32).
+ *   payload [n][nbits * P] u32, one row per message (row pitch: uq_quicfl_packed_words): plane b is words
+ *     [b P, (b + 1) P); bit i % 32 of word i / 32 of plane b is bit b of X_i (uq_rht_sign_bits' numbering);
+ *     every bit that names no coordinate is 0 (bits >= D when D < 32).  X must lie in [0, 2^nbits): a value
+ *     outside sets UQ_QFL_X_RANGE in info[j] and is stored as 0.
+ *   exact_index [n][D] int32: row j's exact coordinates, ascending, in its first exact_count[j] entries, beside
+ *     the compact exact_vals [n][D] f32 (exact_layout 1) and exact_count [n]; a packed message has no mask.
+ *   payload_bits [n] int64 = nbits D + 64 exact_count[j].
+ * uq_quicfl_packed_words: host only; D not a power of two, D > 2^28 or nbits outside 1..4 return UQ_E_INVALID.
+ * uq_quicfl_pack_x: X [n][D] int64 / uint8 / int32 (x_kind 0 / 1 / 2) and exact_mask [n][D] u8 (or NULL: no
+ *   exact coordinate) -> payload, exact_index, exact_count, payload_bits (or NULL), info (or NULL; written).
+ * uq_quicfl_unpack_x: payload and the list (exact_index and exact_count, or both NULL) -> X_u8 [n][D] and
+ *   exact_mask [n][D] u8; a malformed list (below) sets UQ_QFL_BAD_EXACT in info[j] (or NULL; written).
+ * uq_quicfl_compress_packed_f32: uq_quicfl_compress_f32 with payload (nbits planes), exact_index and payload_bits
+ *   in place of X, x_kind and exact_mask: the same generators, px_state_out, flags, side stream and dispatch
+ *   plan, exact_vals / exact_count / scale the same bits.  Workspace: uq_quicfl_packed_workspace_bytes.
+ * uq_quicfl_receive_packed_f32: uq_quicfl_receive_ws_f32 on such a message (the list: all three or all NULL);
+ *   out the same bits.  A row whose list is malformed -- exact_count outside 0..D, an index outside 0..D-1, or
+ *   indices not strictly ascending -- gets UQ_QFL_BAD_EXACT in info[j]; nothing is written outside its row.
+ *   Workspace (required): uq_quicfl_receive_packed_workspace_bytes.
+ * Test hooks: uq_test_set_quicfl_packed_hooks, process-wide, bit 0 sends every packed call through the u8
+ *   kernels on rows in the workspace and the converters (returns the previous flags);
+ *   uq_test_last_quicfl_packed_plan: of this thread's last packed call of that side, 4 int64 of which
+ *   min(cap, 4) are written: [0] nbits (0: it launched nothing) [1] form: 1 the rounds write / read the planes
+ *   themselves, 2 the converter path [2] P [3] the row pitch.  The QUIC-FL plan (uq_test_last_quicfl_plan) of a
+ *   packed call is the u8 call's of its shape. */
+int uq_test_set_quicfl_packed_hooks(int flags);
+int uq_test_last_quicfl_packed_plan(int32_t side, int64_t* plan_out, int32_t cap);
+int uq_quicfl_packed_words(int64_t D, int32_t nbits, int64_t* pitch_words);
+int uq_quicfl_pack_x(const void* X, int32_t x_kind, int64_t n, int64_t D, int32_t nbits, const uint8_t* exact_mask,
+                     uint32_t* payload, int32_t* exact_index, int32_t* exact_count, int64_t* payload_bits, int32_t* info,
+                     void* stream);
+int uq_quicfl_unpack_x(const uint32_t* payload, int64_t n, int64_t D, int32_t nbits, const int32_t* exact_index,
+                       const int32_t* exact_count, uint8_t* X_u8, uint8_t* exact_mask, int32_t* info, void* stream);
+int uq_quicfl_packed_workspace_bytes(int64_t n, int64_t dim, size_t* bytes_out);
+int uq_quicfl_compress_packed_f32(const float* x, int64_t n, int64_t dim, const int8_t* signs, const int32_t* sign_row,
+                                  const float* table_xp, const uint32_t* table_packed, int64_t table_numel, int32_t h_len,
+                                  float delta, const int32_t* prng_seeds, const uint32_t* px_state, const int32_t* px_seeds,
+                                  uint32_t* px_state_out, uint32_t* payload, int32_t nbits, int32_t* exact_index,
+                                  float* exact_vals, int32_t* exact_count, int64_t* payload_bits, float* scale, int32_t* info,
+                                  void* ws, size_t ws_bytes, void* stream);
+int uq_quicfl_receive_packed_workspace_bytes(int64_t n, int64_t D, size_t* bytes_out);
+int uq_quicfl_receive_packed_f32(const uint32_t* payload, int32_t nbits, int64_t n, int64_t D, const float* recv_table,
+                                 int32_t table_rows, int32_t h_len, const int32_t* prng_seeds, const int32_t* exact_index,
+                                 const float* exact_vals, const int32_t* exact_count, const float* scale, float* out,
+                                 int32_t* info, void* ws, size_t ws_bytes, void* stream);
 /* xxHash64 of `len` bytes (AS:457 hashes str(seed) with seed 0); host-only, no GPU. */
 uint64_t uq_xxh64(const void* data, size_t len, uint64_t seed);
 int uq_eden_workspace_bytes(int64_t n, int64_t dim, size_t* bytes_out);

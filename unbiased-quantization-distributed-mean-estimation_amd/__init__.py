@@ -17,7 +17,8 @@ from .biased import Type_biased_quantize, biased_quantize, biased_quantize_encod
 from .eden import (EDEN_quantize_Hadamard, eden_quantize, eden_compress, eden_decompress, EdenMessage, rht_signs,
                    randomized_hadamard_transform, randomized_inverse_hadamard_transform, eden_pack, eden_unpack)
 from .quicfl import (QuicFLReceiver, QuicFLSender, QuicFLMessages, QUICFL_quantize, quicfl_compress,
-                     quicfl_decompress, quicfl_decompress_messages, quicfl_quantize, set_tables_prefix)
+                     quicfl_decompress, quicfl_decompress_messages, quicfl_quantize, quicfl_pack, quicfl_unpack,
+                     set_tables_prefix)
 from .rand_schemes import Scalar_quantize, DRIVE_quantize_Hadamard, scalar_quantize, drive_quantize, drive_words
 from .kashin import (Kashin_quantize, kashin_quantize, kashin_compress, kashin_decompress, kashin_padded_dim,
                      KashinMessage)
@@ -32,7 +33,7 @@ __all__ = [
     "Kashin_quantize", "kashin_quantize", "kashin_compress", "kashin_decompress", "kashin_padded_dim", "KashinMessage",
     "Scalar_quantize", "DRIVE_quantize_Hadamard", "scalar_quantize", "drive_quantize", "drive_words",
     "QuicFLReceiver", "QuicFLSender", "QuicFLMessages", "QUICFL_quantize", "quicfl_compress", "quicfl_decompress",
-    "quicfl_decompress_messages", "quicfl_quantize", "set_tables_prefix",
+    "quicfl_decompress_messages", "quicfl_quantize", "quicfl_pack", "quicfl_unpack", "set_tables_prefix",
     "RATE_TABLE", "rate_to_m", "Type_unbiased_quantize", "quantize_dequantize", "client_mean",
     "quantize_mean", "l1_torch_order", "draw_uniforms", "set_torch_threads", "get_torch_threads",
     "check_status", "UQError", "load_library", "library_path", "shard_range", "sharded_client_mean",

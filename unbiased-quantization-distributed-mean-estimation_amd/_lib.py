@@ -75,6 +75,24 @@ SIGNATURES = {
                                               _p, _p, _p, _p, _sz, _p]),
     "uq_quicfl_compress_f32": (ctypes.c_int, [_p, _i64, _i64, _p, _p, _p, _p, _i64, _i32, _f32, _p, _p, _p, _p, _p, _i32,
                                               _p, _p, _p, _p, _p, _p, _sz, _p]),
+    # the packed message form
+    "uq_test_set_quicfl_packed_hooks": (ctypes.c_int, [ctypes.c_int]),
+    "uq_test_last_quicfl_packed_plan": (ctypes.c_int, [_i32, _p, _i32]),
+    "uq_quicfl_packed_words": (ctypes.c_int, [_i64, _i32, ctypes.POINTER(_i64)]),
+    # X, x_kind, n, D, nbits, exact_mask, payload, exact_index, exact_count, payload_bits, info, stream
+    "uq_quicfl_pack_x": (ctypes.c_int, [_p, _i32, _i64, _i64, _i32, _p, _p, _p, _p, _p, _p, _p]),
+    # payload, n, D, nbits, exact_index, exact_count, X_u8, exact_mask, info, stream
+    "uq_quicfl_unpack_x": (ctypes.c_int, [_p, _i64, _i64, _i32, _p, _p, _p, _p, _p, _p]),
+    "uq_quicfl_packed_workspace_bytes": (ctypes.c_int, [_i64, _i64, ctypes.POINTER(_sz)]),
+    # uq_quicfl_compress_f32's head and generators, then payload, nbits, exact_index, exact_vals, exact_count,
+    # payload_bits, scale, info, ws, ws_bytes, stream
+    "uq_quicfl_compress_packed_f32": (ctypes.c_int, [_p, _i64, _i64, _p, _p, _p, _p, _i64, _i32, _f32, _p, _p, _p, _p, _p,
+                                                     _i32, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "uq_quicfl_receive_packed_workspace_bytes": (ctypes.c_int, [_i64, _i64, ctypes.POINTER(_sz)]),
+    # payload, nbits, n, D, recv_table, table_rows, h_len, prng_seeds, exact_index, exact_vals, exact_count, scale,
+    # out, info, ws, ws_bytes, stream
+    "uq_quicfl_receive_packed_f32": (ctypes.c_int, [_p, _i32, _i64, _i64, _p, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p,
+                                                    _sz, _p]),
     "uq_xxh64": (ctypes.c_uint64, [ctypes.c_char_p, _sz, ctypes.c_uint64]),
     "uq_eden_workspace_bytes": (ctypes.c_int, [_i64, _i64, ctypes.POINTER(_sz)]),
     "uq_eden_compress_f32": (ctypes.c_int, [_p, _i64, _i64, _i32, _p, _p, _p, _p, _p, _sz, _p]),

@@ -1,6 +1,7 @@
 // uq_quicfl.hip — QUIC-FL: the dispatch plan, the launchers of uq_quicfl_kernels.h and the C API
 // of the sender (uq_quicfl_compress_f32, uq_quicfl_quantize_f32) and the receiver
-// (uq_quicfl_receive_*), and uq_xxh64 (the sender's prng seed).  The RHT and the norm run in
+// (uq_quicfl_receive_*), the packed message form of both (uq_quicfl_*_packed_f32, uq_quicfl_pack_x /
+// uq_quicfl_unpack_x), and uq_xxh64 (the sender's prng seed).  The RHT and the norm run in
 // uq_eden.hip.
 #include <hip/hip_runtime.h>
 
@@ -21,6 +22,8 @@
 
 // uq_test_set_quicfl_hooks (include/uq_dme.h); each entry point loads it once, into its plan
 static std::atomic<int> g_quicfl_hooks{0};
+// uq_test_set_quicfl_packed_hooks; each packed entry point loads it once
+static std::atomic<int> g_quicfl_packed_hooks{0};
 
 namespace {
 
@@ -123,12 +126,15 @@ int export_plan(const QflPlan& p, int64_t* out, int32_t cap) {
 // compile-time constant: f(XK) launches the instance it names; with W2 behind it for the
 // sender's runs.  (2, 0, 1 is the order the sender's instances have always been emitted in;
 // another order moves the padding between kernels, and with it tools/kernel_table.py's hashes.)
+// 3: the packed message's instances (internal: no entry point takes it as an x_kind), emitted in front of them:
+// the last instance of the unit has no padding behind it, and stays the last.
 template <int K>
 using Xk = std::integral_constant<int, K>;
 
 template <class F>
 void select_xk(int32_t x_kind, F&& f) {
-    if (x_kind == 2) f(Xk<2>{});
+    if (x_kind == 3) f(Xk<3>{});
+    else if (x_kind == 2) f(Xk<2>{});
     else if (x_kind == 0) f(Xk<0>{});
     else f(Xk<1>{});
 }
@@ -239,8 +245,10 @@ static int quicfl_recv_jump(const QflRecvArgs& r, int32_t x_kind, const QflPlan&
     ra.runinfo = (int32_t*)(parts + (size_t)n * P.R * kMjParts * kMtN);
     ra.R = P.R;
     ra.L = P.L;
-    hipLaunchKernelGGL(quicfl_recv_count_kernel, wave_grid(n * P.R), kWaveBlock, 0, st, r, ra);
-    if ((rc = launched("quicfl_recv_count_kernel launch"))) return rc;
+    if (x_kind != 3) {                                   // (a packed message has no mask to count)
+        hipLaunchKernelGGL(quicfl_recv_count_kernel, wave_grid(n * P.R), kWaveBlock, 0, st, r, ra);
+        if ((rc = launched("quicfl_recv_count_kernel launch"))) return rc;
+    }
     select_xk(x_kind, [&](auto XK) {
         hipLaunchKernelGGL(quicfl_recv_runs_kernel<XK()>, wave_grid(n * P.R), kWaveBlock, 0, st, r, ra);
     });
@@ -249,16 +257,18 @@ static int quicfl_recv_jump(const QflRecvArgs& r, int32_t x_kind, const QflPlan&
     return launched("quicfl_recv_fin_kernel launch");
 }
 
-int uq_quicfl_receive_ws_f32(const void* X, int32_t x_kind, int64_t n, int64_t D, const float* recv_table,
-                             int32_t table_rows, int32_t h_len, const int32_t* prng_seeds, const uint8_t* exact_mask,
-                             const float* exact_vals, int32_t exact_layout, const int32_t* exact_count,
-                             const float* scale, float* out, int32_t* info, void* ws, size_t ws_bytes, void* stream) {
+// The receiver of every entry point.  x_kind 3 (the packed entry point only: nbits planes per payload
+// row in X, no mask and no exact values in the rounds, no counting pass).
+static int quicfl_receive(const void* X, int32_t x_kind, int32_t nbits, int64_t n, int64_t D, const float* recv_table,
+                          int32_t table_rows, int32_t h_len, const int32_t* prng_seeds, const uint8_t* exact_mask,
+                          const float* exact_vals, int32_t exact_layout, const int32_t* exact_count,
+                          const float* scale, float* out, int32_t* info, void* ws, size_t ws_bytes, void* stream) {
     const int hooks = g_quicfl_hooks.load();
     t_last_plan[UQ_QFL_RECEIVER] = QflPlan{};
     if (n < 0 || D < 0) return fail(UQ_E_INVALID, "n and D must be >= 0");
     if (n > 65535) return fail(UQ_E_INVALID, "at most 65535 clients per call");
     if (D > ((int64_t)1 << 28)) return fail(UQ_E_INVALID, "at most 2^28 coordinates per message");
-    if (x_kind < 0 || x_kind > 2) return fail(UQ_E_INVALID, "x_kind must be 0 (int64), 1 (uint8) or 2 (int32)");
+    if (x_kind < 0 || x_kind > 2 + (nbits > 0)) return fail(UQ_E_INVALID, "x_kind must be 0 (int64), 1 (uint8) or 2 (int32)");
     if (exact_layout != 0 && exact_layout != 1) return fail(UQ_E_INVALID, "exact_layout must be 0 (dense) or 1 (compact)");
     if (n == 0 || D == 0) return UQ_OK;
     if (!X || !recv_table || !prng_seeds || !scale || !out) return fail(UQ_E_INVALID, "null pointer");
@@ -279,6 +289,7 @@ int uq_quicfl_receive_ws_f32(const void* X, int32_t x_kind, int64_t n, int64_t D
     r.exact_mask = exact_mask;
     r.exact_vals = exact_vals;
     r.compact = exact_layout;
+    r.nbits = nbits;
     r.exact_count = exact_count;
     r.scale = scale;
     r.out = out;
@@ -293,6 +304,14 @@ int uq_quicfl_receive_ws_f32(const void* X, int32_t x_kind, int64_t n, int64_t D
     }
     select_xk(x_kind, [&](auto XK) { hipLaunchKernelGGL(quicfl_recv_wave_kernel<XK()>, wave_grid(n), kWaveBlock, 0, st, r); });
     return launched("quicfl_recv_wave_kernel launch");
+}
+
+int uq_quicfl_receive_ws_f32(const void* X, int32_t x_kind, int64_t n, int64_t D, const float* recv_table,
+                             int32_t table_rows, int32_t h_len, const int32_t* prng_seeds, const uint8_t* exact_mask,
+                             const float* exact_vals, int32_t exact_layout, const int32_t* exact_count,
+                             const float* scale, float* out, int32_t* info, void* ws, size_t ws_bytes, void* stream) {
+    return quicfl_receive(X, x_kind, 0, n, D, recv_table, table_rows, h_len, prng_seeds, exact_mask, exact_vals, exact_layout,
+                          exact_count, scale, out, info, ws, ws_bytes, stream);
 }
 
 int uq_quicfl_prepare_f32(const int32_t* X, int64_t n, int64_t D, const float* recv_table, int32_t table_rows,
@@ -366,7 +385,22 @@ static int quicfl_send_side(const QflSendArgs& q, const QflPlan& P, const uint32
 // The plan's form on the caller's stream, after the join: KQ1j + KQ1f (every run of every message
 // at once from the jumped blocks), KQ1t (scouts + runs in one workgroup per message) or KQ1 (a
 // wave per message).  x_kind 2: the fused instances.
-static int launch_quicfl_send(QflSendArgs& q, int32_t x_kind, const QflPlan& P, uint32_t* jump, hipStream_t st) {
+static int launch_quicfl_form(QflSendArgs& q, int32_t x_kind, const QflPlan& P, uint32_t* jump, hipStream_t st);
+// ... and, behind a packed form (x_kind 3), KQ1p: the jump form's indices into index order, payload_bits
+static int launch_quicfl_send(QflSendArgs& q, int32_t x_kind, const QflPlan& P, uint32_t* jump, int64_t* payload_bits,
+                              hipStream_t st) {
+    int rc = launch_quicfl_form(q, x_kind, P, jump, st);
+    if (rc || x_kind != 3) return rc;
+    QflRunArgs ra{};
+    if (P.form == UQ_QFL_FORM_JUMP) {
+        ra.runinfo = (int32_t*)(jump + (size_t)q.n * 2 * kMjX + (size_t)q.n * P.R * 3 * kMjParts * kMtN);
+        ra.R = P.R;
+        ra.L = P.L;
+    }
+    hipLaunchKernelGGL(quicfl_send_fin_packed_kernel, wave_grid(q.n), kWaveBlock, 0, st, q, ra, payload_bits);
+    return launched("quicfl_send_fin_packed_kernel launch");
+}
+static int launch_quicfl_form(QflSendArgs& q, int32_t x_kind, const QflPlan& P, uint32_t* jump, hipStream_t st) {
     const int64_t n = q.n;
     if (P.form == UQ_QFL_FORM_JUMP) {
         QflRunArgs ra{};
@@ -414,6 +448,7 @@ struct QflSendCall {
     void* ws;
     size_t ws_bytes;
     void* stream;
+    size_t ws_extra = 0;        // bytes the entry point keeps behind the sender's own workspace
 };
 
 // The sender of both entry points: the shared checks, the plan, the side-stream work, the RHT
@@ -422,7 +457,7 @@ struct QflSendCall {
 // order.  *rot: the rotated vectors (null when nothing ran), into which a fused call
 // (q.rtab set) also writes the receiver's values.
 static int quicfl_send(const QflSendCall& c, const char* own_error, bool own_null, QflSendArgs q, int32_t x_kind,
-                       float** rot) {
+                       float** rot, int64_t* payload_bits = nullptr) {
     const int hooks = g_quicfl_hooks.load();
     t_last_plan[UQ_QFL_SENDER] = QflPlan{};
     *rot = nullptr;
@@ -440,7 +475,7 @@ static int quicfl_send(const QflSendCall& c, const char* own_error, bool own_nul
     const RhtLayout w = rht_layout(n, dim);
     const size_t joff = quicfl_jump_off(n, dim);
     const QflPlan P = qfl_plan(UQ_QFL_SENDER, n, w.D, hooks, SIZE_MAX);
-    if (!c.ws || c.ws_bytes < joff + P.jump_bytes) return fail(UQ_E_WORKSPACE, "workspace too small");
+    if (!c.ws || c.ws_bytes < joff + P.jump_bytes + c.ws_extra) return fail(UQ_E_WORKSPACE, "workspace too small");
     t_last_plan[UQ_QFL_SENDER] = P;
     hipStream_t st = (hipStream_t)c.stream;
     char* wsb = (char*)c.ws;
@@ -475,7 +510,7 @@ static int quicfl_send(const QflSendCall& c, const char* own_error, bool own_nul
     if (fk && (rc = fk->join())) return rc;
     q.rot = *rot;
     if (q.rtab) q.pre = *rot;                // in place: a coordinate's rot is loaded a round before its value is stored
-    return launch_quicfl_send(q, x_kind, P, jump, st);
+    return launch_quicfl_send(q, x_kind, P, jump, payload_bits, st);
 }
 
 int uq_quicfl_compress_f32(const float* x, int64_t n, int64_t dim, const int8_t* signs, const int32_t* sign_row,
@@ -515,6 +550,203 @@ int uq_quicfl_quantize_f32(const float* x, int64_t n, int64_t dim, const int8_t*
                                !recv_table || !out, q, 2, &rot);        // (2: the fused instances)  AS:455-503, 526-532
     if (rc || !rot) return rc;
     return rht_inverse(rot, out, n, rht_layout(n, dim).D, dim, signs, sign_row, (hipStream_t)stream);   // AS:533-535
+}
+
+// ---- the packed message (it replaces nothing of the reference: AS:494-503 keeps X and the mask) ----
+// Form of a packed call: the sender's and the receiver's own rounds write / read the planes (fused), or
+// the u8 kernels run on X and mask rows in the workspace and the converters stand between them and the
+// message (packed hook bit 0).  DESIGN §4.4 has the measurement behind "fused everywhere".
+#define UQ_QFL_PACKED_FUSED 1
+#define UQ_QFL_PACKED_CONVERTER 2
+extern "C++" {
+namespace {
+struct QflPackedPlan {
+    int32_t nbits = 0, form = 0;
+    int64_t P = 0, pitch = 0;
+};
+thread_local QflPackedPlan t_last_qpacked[2];        // uq_test_last_quicfl_packed_plan, per side
+
+// nbits and D of a packed row (host only): the message of the first failed check, or null
+const char* qfl_packed_shape_error(int64_t D, int32_t nbits) {
+    if (nbits < 1 || nbits > 4) return "nbits must be 1..4";
+    if (D < 1 || (D & (D - 1))) return "D must be a power of two";
+    if (D > ((int64_t)1 << 28)) return "at most 2^28 coordinates per message";
+    return nullptr;
+}
+QflPackedPlan qfl_packed_plan(int64_t D, int32_t nbits, int hooks) {
+    QflPackedPlan k;
+    k.nbits = nbits;
+    k.form = (hooks & 1) ? UQ_QFL_PACKED_CONVERTER : UQ_QFL_PACKED_FUSED;
+    k.P = (D + 31) / 32;
+    k.pitch = nbits * k.P;
+    return k;
+}
+// the converter path's rows behind a u8 call's own workspace: X [n][D] u8, mask [n][D] u8, flags [n]
+size_t qfl_conv_bytes(int64_t n, int64_t D) { return up256(2 * (size_t)n * (size_t)D) + up256((size_t)n * sizeof(int32_t)); }
+}  // namespace
+}  // extern "C++"
+
+int uq_test_set_quicfl_packed_hooks(int flags) { return g_quicfl_packed_hooks.exchange(flags & 1); }
+
+int uq_test_last_quicfl_packed_plan(int32_t side, int64_t* plan_out, int32_t cap) {
+    if (side != UQ_QFL_SENDER && side != UQ_QFL_RECEIVER) return fail(UQ_E_INVALID, "side must be 0 (sender) or 1 (receiver)");
+    if (!plan_out || cap < 0) return fail(UQ_E_INVALID, "null plan output");
+    const QflPackedPlan& k = t_last_qpacked[side];
+    const int64_t f[4] = {k.nbits, k.form, k.P, k.pitch};
+    for (int i = 0; i < std::min<int32_t>(cap, 4); ++i) plan_out[i] = f[i];
+    return UQ_OK;
+}
+
+int uq_quicfl_packed_words(int64_t D, int32_t nbits, int64_t* pitch_words) {
+    if (!pitch_words) return fail(UQ_E_INVALID, "null pitch_words");
+    if (const char* e = qfl_packed_shape_error(D, nbits)) return fail(UQ_E_INVALID, e);
+    *pitch_words = nbits * ((D + 31) / 32);
+    return UQ_OK;
+}
+
+int uq_quicfl_pack_x(const void* X, int32_t x_kind, int64_t n, int64_t D, int32_t nbits, const uint8_t* exact_mask,
+                     uint32_t* payload, int32_t* exact_index, int32_t* exact_count, int64_t* payload_bits, int32_t* info,
+                     void* stream) {
+    if (n < 0) return fail(UQ_E_INVALID, "n must be >= 0");
+    if (n > 65535) return fail(UQ_E_INVALID, "at most 65535 messages per call");
+    if (x_kind < 0 || x_kind > 2) return fail(UQ_E_INVALID, "x_kind must be 0 (int64), 1 (uint8) or 2 (int32)");
+    if (const char* e = qfl_packed_shape_error(D, nbits)) return fail(UQ_E_INVALID, e);
+    if (n == 0) return UQ_OK;
+    if (!X || !payload || !exact_index || !exact_count) return fail(UQ_E_INVALID, "null pointer");
+    hipLaunchKernelGGL(quicfl_pack_x_kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, X, x_kind, D, nbits, exact_mask,
+                       payload, exact_index, exact_count, payload_bits, info, 0);
+    return launched("quicfl_pack_x_kernel launch");
+}
+
+int uq_quicfl_unpack_x(const uint32_t* payload, int64_t n, int64_t D, int32_t nbits, const int32_t* exact_index,
+                       const int32_t* exact_count, uint8_t* X_u8, uint8_t* exact_mask, int32_t* info, void* stream) {
+    if (n < 0) return fail(UQ_E_INVALID, "n must be >= 0");
+    if (n > 65535) return fail(UQ_E_INVALID, "at most 65535 messages per call");
+    if (const char* e = qfl_packed_shape_error(D, nbits)) return fail(UQ_E_INVALID, e);
+    if (n == 0) return UQ_OK;
+    if (!payload || !X_u8 || !exact_mask) return fail(UQ_E_INVALID, "null pointer");
+    if ((exact_index == nullptr) != (exact_count == nullptr)) return fail(UQ_E_INVALID, "exact_index and exact_count go together");
+    hipLaunchKernelGGL(quicfl_unpack_x_kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, payload, D, nbits, exact_index,
+                       exact_count, X_u8, exact_mask, info);
+    return launched("quicfl_unpack_x_kernel launch");
+}
+
+int uq_quicfl_packed_workspace_bytes(int64_t n, int64_t dim, size_t* bytes_out) {
+    const int rc = uq_quicfl_workspace_bytes(n, dim, bytes_out);
+    if (rc) return rc;
+    *bytes_out = up256(*bytes_out) + qfl_conv_bytes(n, rht_layout(n, dim).D);
+    return UQ_OK;
+}
+
+int uq_quicfl_compress_packed_f32(const float* x, int64_t n, int64_t dim, const int8_t* signs, const int32_t* sign_row,
+                                  const float* table_xp, const uint32_t* table_packed, int64_t table_numel, int32_t h_len,
+                                  float delta, const int32_t* prng_seeds, const uint32_t* px_state, const int32_t* px_seeds,
+                                  uint32_t* px_state_out, uint32_t* payload, int32_t nbits, int32_t* exact_index,
+                                  float* exact_vals, int32_t* exact_count, int64_t* payload_bits, float* scale, int32_t* info,
+                                  void* ws, size_t ws_bytes, void* stream) {
+    const int hooks = g_quicfl_packed_hooks.load();
+    t_last_qpacked[UQ_QFL_SENDER] = QflPackedPlan{};
+    t_last_plan[UQ_QFL_SENDER] = QflPlan{};
+    const char* own_error = nbits < 1 || nbits > 4 ? "nbits must be 1..4" : nullptr;
+    const bool own_null = !payload || !exact_index || !exact_vals || !exact_count || !payload_bits || !scale;
+    // the u8 call's workspace, then the converter path's rows (whichever form runs: one size per shape)
+    size_t base0 = 0, base = 0;
+    int64_t D = 0;
+    if (n > 0 && dim > 0 && n <= 65535 && dim <= ((int64_t)1 << 28)) {
+        if (const int rc = uq_quicfl_workspace_bytes(n, dim, &base0)) return rc;
+        base = up256(base0);
+        D = rht_layout(n, dim).D;
+    }
+    const QflSendCall c{x, n, dim, signs, sign_row, table_xp, table_packed, table_numel, h_len, delta, prng_seeds,
+                        px_state, px_seeds, px_state_out, scale, info, ws, ws_bytes, stream,
+                        base - base0 + qfl_conv_bytes(n > 0 ? n : 0, D)};
+    const QflPackedPlan k = qfl_packed_plan(D, nbits, hooks);
+    float* rot = nullptr;
+    QflSendArgs q{};
+    q.ev = exact_vals;
+    q.ecount = exact_count;
+    if (k.form == UQ_QFL_PACKED_FUSED) {
+        q.X = payload;
+        q.x_kind = 3;
+        q.nbits = nbits;
+        q.eidx = exact_index;
+        const int rc = quicfl_send(c, own_error, own_null, q, 3, &rot, payload_bits);
+        if (!rc && rot) t_last_qpacked[UQ_QFL_SENDER] = k;
+        return rc;
+    }
+    // the converter path: the u8 sender into the workspace's rows, then the converter (info ORed into)
+    uint8_t* Xu = (uint8_t*)ws + base;
+    uint8_t* mk = Xu + (size_t)(n > 0 ? n : 0) * D;
+    q.X = Xu;
+    q.x_kind = 1;
+    q.mask = mk;
+    int rc = quicfl_send(c, own_error, own_null, q, 1, &rot);
+    if (rc || !rot) return rc;
+    hipLaunchKernelGGL(quicfl_pack_x_kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, (const void*)Xu, 1, D, nbits,
+                       (const uint8_t*)mk, payload, exact_index, exact_count, payload_bits, info, 1);
+    if ((rc = launched("quicfl_pack_x_kernel launch"))) return rc;
+    t_last_qpacked[UQ_QFL_SENDER] = k;
+    return UQ_OK;
+}
+
+int uq_quicfl_receive_packed_workspace_bytes(int64_t n, int64_t D, size_t* bytes_out) {
+    const int rc = uq_quicfl_receive_workspace_bytes(n, D, bytes_out);
+    if (rc) return rc;
+    *bytes_out = up256(*bytes_out) + qfl_conv_bytes(n, D);
+    return UQ_OK;
+}
+
+int uq_quicfl_receive_packed_f32(const uint32_t* payload, int32_t nbits, int64_t n, int64_t D, const float* recv_table,
+                                 int32_t table_rows, int32_t h_len, const int32_t* prng_seeds, const int32_t* exact_index,
+                                 const float* exact_vals, const int32_t* exact_count, const float* scale, float* out,
+                                 int32_t* info, void* ws, size_t ws_bytes, void* stream) {
+    const int hooks = g_quicfl_packed_hooks.load();
+    t_last_qpacked[UQ_QFL_RECEIVER] = QflPackedPlan{};
+    t_last_plan[UQ_QFL_RECEIVER] = QflPlan{};
+    if (n < 0) return fail(UQ_E_INVALID, "n must be >= 0");
+    if (n > 65535) return fail(UQ_E_INVALID, "at most 65535 clients per call");
+    if (const char* e = qfl_packed_shape_error(D, nbits)) return fail(UQ_E_INVALID, e);
+    if (n == 0) return UQ_OK;
+    if (!payload || !recv_table || !prng_seeds || !scale || !out) return fail(UQ_E_INVALID, "null pointer");
+    if ((exact_index == nullptr) != (exact_vals == nullptr) || (exact_index == nullptr) != (exact_count == nullptr))
+        return fail(UQ_E_INVALID, "exact_index, exact_vals and exact_count go together");
+    size_t base = 0;
+    if (const int rc = uq_quicfl_receive_workspace_bytes(n, D, &base)) return rc;
+    base = up256(base);
+    if (!ws || ws_bytes < base + qfl_conv_bytes(n, D)) return fail(UQ_E_WORKSPACE, "workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    const QflPackedPlan k = qfl_packed_plan(D, nbits, hooks);
+    int rc;
+    if (k.form == UQ_QFL_PACKED_FUSED) {
+        // the rounds on the planes (no mask, no exact values), then the exact coordinates from their list
+        if ((rc = quicfl_receive(payload, 3, nbits, n, D, recv_table, table_rows, h_len, prng_seeds, nullptr, nullptr, 0, nullptr,
+                                 scale, out, info, ws, base, stream)))
+            return rc;
+        if (exact_index) {
+            hipLaunchKernelGGL(quicfl_exact_scatter_kernel, dim3((unsigned)n), dim3(256), 0, st, exact_index, exact_vals,
+                               exact_count, scale, out, info, D);
+            if ((rc = launched("quicfl_exact_scatter_kernel launch"))) return rc;
+        }
+    } else {
+        // the converter path: X and the mask rebuilt in the workspace, the u8 receiver on them; the list's
+        // own check (order included, which a mask cannot show) joins the receiver's flags
+        char* conv = (char*)ws + base;
+        uint8_t* Xu = (uint8_t*)conv;
+        uint8_t* mk = Xu + (size_t)n * D;
+        int32_t* linfo = (int32_t*)(conv + up256(2 * (size_t)n * (size_t)D));
+        hipLaunchKernelGGL(quicfl_unpack_x_kernel, dim3((unsigned)n), dim3(256), 0, st, payload, D, nbits, exact_index, exact_count,
+                           Xu, mk, linfo);
+        if ((rc = launched("quicfl_unpack_x_kernel launch"))) return rc;
+        if ((rc = quicfl_receive(Xu, 1, 0, n, D, recv_table, table_rows, h_len, prng_seeds, exact_index ? mk : nullptr,
+                                 exact_index ? exact_vals : nullptr, 1, exact_count, scale, out, info, ws, base, stream)))
+            return rc;
+        if (info) {
+            hipLaunchKernelGGL(quicfl_or_info_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, info, (const int32_t*)linfo, n);
+            if ((rc = launched("quicfl_or_info_kernel launch"))) return rc;
+        }
+    }
+    t_last_qpacked[UQ_QFL_RECEIVER] = k;
+    return UQ_OK;
 }
 
 // xxHash64 (the public XXH64 algorithm), for AS:457's prng seed

@@ -52,14 +52,18 @@ struct QflSendArgs {
     int32_t h_len;
     float delta;                // f32(data['delta'])
     float sqrtD;                // f32(np.sqrt(D))
+    int32_t nbits;              // XK 3 (the packed message): planes per payload row
     const int32_t* prng_seeds;  // [n] local generator seeds (AS:457)
     const uint32_t* px_state;   // [n][2 + 624] global generator state per message, or null
     const int32_t* px_seeds;    // [n] seeds of fresh generators (when px_state is null)
     uint32_t* px_state_out;     // [n][2 + 624] state after the D draws, or null
     uint8_t* hbuf;              // [n][D] scratch: h
-    void* X;                    // [n][D] int64 (x_kind 0) or uint8 (x_kind 1)
+    void* X;                    // [n][D] int64 (x_kind 0) or uint8 (x_kind 1); XK 3: payload rows [n][nbits * P] u32
     int32_t x_kind;
-    uint8_t* mask;              // [n][D] exact_indeces
+    union {
+        uint8_t* mask;          // [n][D] exact_indeces
+        int32_t* eidx;          // XK 3: [n][D] the exact coordinates' indices, beside ev (no mask is written)
+    };
     float* ev;                  // [n][D] exact values, compacted per message (first ecount[j])
     int32_t* ecount;            // [n]
     float* scale;               // [n]
@@ -105,6 +109,8 @@ struct QflCtx {
     int32_t numel;
     uint32_t h_len;
     bool hpow2;
+    int32_t* ix;                // XK 3: the message's index row
+    uint32_t nb, Pw;            // XK 3: planes, words per plane
 };
 
 template <int XK>
@@ -122,9 +128,16 @@ __device__ __forceinline__ QflCtx qfl_ctx(const QflSendArgs& a, int64_t j, int32
     c.rr = make_rsrc(a.rot + c.row, Du * 4u);
     c.rh = make_rsrc(a.hbuf + c.row, Du);
     c.rm = make_rsrc(a.mask + c.row, Du);
+    // XK 3: the packed message (payload planes, index row; no mask)
+    c.nb = (uint32_t)a.nbits;
+    c.Pw = (Du + 31u) / 32u;
+    c.ix = a.eidx + c.row;
     // XK 2: the fused receiver (QUICFL_quantize, a.pre set): no X / mask / exact values written,
     // and the compiler drops those paths (and their scalar state) from the instance
-    c.rX = make_rsrc(XK == 0 ? (void*)((int64_t*)a.X + c.row) : (void*)((uint8_t*)a.X + c.row), XK == 0 ? Du * 8u : Du);
+    if (XK == 3)
+        c.rX = make_rsrc((uint32_t*)a.X + j * (int64_t)(c.nb * c.Pw), c.nb * c.Pw * 4u);
+    else
+        c.rX = make_rsrc(XK == 0 ? (void*)((int64_t*)a.X + c.row) : (void*)((uint8_t*)a.X + c.row), XK == 0 ? Du * 8u : Du);
     c.packed = a.tabp != nullptr;
     c.rt = c.packed ? make_rsrc(a.tabp, (uint32_t)a.numel * 4u) : make_rsrc(a.tab, (uint32_t)a.numel * 8u);
     c.sc = (1.0f / a.nrm[j]) * a.sqrtD;                             // AS:466/470 (IEEE 1/x, then f32 mul)
@@ -207,6 +220,7 @@ __device__ __forceinline__ int64_t qfl_pass_b(const QflCtx& c, float* __restrict
     load_in((uint32_t)(c0 * kMtN), I0);
 
     auto finish = [&](const QflRound& r, uint32_t i0) {          // stage 2 of a round (AS:489-490, 494-495)
+        uint32_t hw[4] = {0u, 0u, 0u, 0u};                       // XK 3: halfword `lane` of the round, per plane
 #pragma unroll
         for (int k = 0; k < kMtGroups; ++k) {
             const uint32_t i = i0 + 64u * k + lane;
@@ -237,7 +251,22 @@ __device__ __forceinline__ int64_t qfl_pass_b(const QflCtx& c, float* __restrict
                                                       qf_off(active, i * 4u), 0, 0);   // AS:532 / scale
                 continue;
             }
-            if (XK == 0) {
+            if (XK == 3) {
+                // the group's X bits as wave ballots per plane: the ballot of group k is halfwords
+                // 4 k .. 4 k + 3 of the round (624 = 39 * 16: rounds, groups and runs start on
+                // halfwords of a plane), gathered into lane 4 k + h and stored once per round
+                const bool ok = xf > -1.0f && xf < (float)(1u << c.nb);
+                flags |= (active && !ok) ? UQ_QFL_X_RANGE : 0;
+                const uint32_t xi = ok ? (uint32_t)(int32_t)xf : 0u;
+                const bool mine = (lane >> 2) == k;
+#pragma unroll
+                for (int b = 0; b < 4; ++b) {
+                    if (b < (int)c.nb) {
+                        const uint64_t bal = __ballot(active && ((xi >> b) & 1u));
+                        hw[b] = mine ? (uint32_t)(bal >> (16 * (lane & 3))) & 0xFFFFu : hw[b];
+                    }
+                }
+            } else if (XK == 0) {
                 const bool ok = xf > -9.2e18f && xf < 9.2e18f;
                 flags |= (active && !ok) ? UQ_QFL_X_RANGE : 0;
                 const int64_t xv = ok ? (int64_t)xf : 0;             // AS:490 .long()
@@ -249,10 +278,19 @@ __device__ __forceinline__ int64_t qfl_pass_b(const QflCtx& c, float* __restrict
                 flags |= (active && !ok) ? UQ_QFL_X_RANGE : 0;
                 __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(ok ? (int32_t)xf : 0), c.rX, qf_off(active, i), 0, 0);
             }
-            __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(ex ? 1 : 0), c.rm, qf_off(active, i), 0, 0);
+            if (XK != 3) __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(ex ? 1 : 0), c.rm, qf_off(active, i), 0, 0);
             const uint64_t bal = __ballot(active && ex);            // index order: group k, then lane
             if (active && ex) ev[c.row + ev_base + etot + __popcll(bal & ((1ull << lane) - 1ull))] = r.v[k];
+            if (XK == 3 && active && ex) c.ix[ev_base + etot + __popcll(bal & ((1ull << lane) - 1ull))] = (int32_t)i;
             etot += __popcll(bal);
+        }
+        if (XK == 3) {                                           // aligned halfwords: no store unit is shared with another wave
+            const uint32_t hi = i0 / 16u + (uint32_t)lane;
+            const bool st = lane < kMtN / 16 && hi < 2u * c.Pw;  // (D < 32: the word's upper halfword is written too, 0)
+#pragma unroll
+            for (int b = 0; b < 4; ++b)
+                if (b < (int)c.nb)
+                    __builtin_amdgcn_raw_buffer_store_b16((uint16_t)hw[b], c.rX, qf_off(st, ((uint32_t)b * c.Pw * 2u + hi) * 2u), 0, 0);
         }
     };
 
@@ -580,7 +618,9 @@ quicfl_send_team_kernel(QflSendArgs a) {
             for (int64_t i0 = 0; i0 < n_r; i0 += 64) {   // (base <= src: a downward move, chunk by chunk)
                 const int64_t i = i0 + lane;
                 const float v = i < n_r ? a.ev[c.row + src + i] : 0.f;
+                const int32_t ix = XK == 3 && i < n_r ? c.ix[src + i] : 0;
                 if (i < n_r) a.ev[c.row + base + i] = v;
+                if (XK == 3 && i < n_r) c.ix[base + i] = ix;
             }
             base += n_r;
         }
@@ -941,6 +981,30 @@ quicfl_send_fin_kernel(QflSendArgs a, QflRunArgs ra) {
     }
 }
 
+// KQ1p, behind the packed sender's form (one wave per message): the jump form's runs wrote their
+// exact coordinates' indices beside the values, each run from its own span; they move into index
+// order as KQ1f moves the values (ra.R = 0: another form, already in order).  Then the message's
+// size, payload_bits = nbits D + 64 exact_count.
+__global__ void __launch_bounds__(64 * kQfWavesPerWG)
+quicfl_send_fin_packed_kernel(QflSendArgs a, QflRunArgs ra, int64_t* __restrict__ payload_bits) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t j = (int64_t)blockIdx.x * kQfWavesPerWG + wv;
+    if (j >= a.n) return;
+    int32_t* ix = a.eidx + j * a.D;
+    int64_t base = 0;
+    for (int r = 0; r < ra.R; ++r) {
+        const int64_t src = (int64_t)r * ra.L * kMtN, n_r = ra.runinfo[(j * ra.R + r) * 2];
+        if (src != base)
+            for (int64_t i0 = 0; i0 < n_r; i0 += 64) {   // (base < src: a downward move, chunk by chunk)
+                const int64_t i = i0 + lane;
+                const int32_t v = i < n_r ? ix[src + i] : 0;
+                if (i < n_r) ix[base + i] = v;
+            }
+        base += n_r;
+    }
+    if (lane == 0 && payload_bits) payload_bits[j] = (int64_t)a.nbits * a.D + 64 * (int64_t)a.ecount[j];
+}
+
 // ---- receiver: QuicFLReceiver.decompress before its inverse RHT (AS:526-532) -----------------
 // h = torch.randint(0, h_len, (D,)) of a generator seeded with prng_seed (word % h_len), then
 // v = recv_table.take(X * h_len + h) (AS:530: -numel <= index < numel, negatives wrap, anything
@@ -962,6 +1026,7 @@ struct QflRecvArgs {
     const uint8_t* exact_mask;      // [n][D] or null
     const float* exact_vals;        // [n][D] dense or compact, or null
     int compact;
+    int32_t nbits;                  // XK 3: X is payload rows [n][nbits * P] u32 (no mask, no exact values: the scatter)
     const int32_t* exact_count;     // [n] or null (compact: checked against the mask)
     const float* scale;             // [n]
     float* out;                     // [n][D]
@@ -986,7 +1051,9 @@ __device__ __forceinline__ int32_t qfl_recv_rounds(const QflRecvArgs& a, const f
     const bool compact = a.compact != 0;
     constexpr uint32_t xb = XK == 0 ? 8u : (XK == 1 ? 1u : 4u);  // bytes per X
     // buffer descriptors: branch-free loads (0 beyond D) and stores (dropped beyond D)
-    const __amdgpu_buffer_rsrc_t rXs = make_rsrc((const char*)a.X + row * xb, Du * xb);
+    const uint32_t nb = (uint32_t)a.nbits, Pw = (Du + 31u) / 32u;   // XK 3: planes, words per plane
+    const __amdgpu_buffer_rsrc_t rXs = XK == 3 ? make_rsrc((const uint32_t*)a.X + j * (int64_t)(nb * Pw), nb * Pw * 4u)
+                                               : make_rsrc((const char*)a.X + row * xb, Du * xb);
     const __amdgpu_buffer_rsrc_t rmk = make_rsrc(a.exact_mask ? (const void*)(a.exact_mask + row) : a.X,
                                                  a.exact_mask ? Du : 0u);
     const __amdgpu_buffer_rsrc_t rvl = make_rsrc(a.exact_vals ? (const void*)(a.exact_vals + row) : a.X,
@@ -999,9 +1066,18 @@ __device__ __forceinline__ int32_t qfl_recv_rounds(const QflRecvArgs& a, const f
         int64_t x[kMtGroups];
         uint32_t m[kMtGroups];
         float v[kMtGroups];
+        uint32_t pw[XK == 3 ? 4 : 0];   // XK 3: halfword `lane` of the round, per plane
     };
     Set S0, S1, S2;
     auto load_x = [&](uint32_t i0, Set& o) {
+        if constexpr (XK == 3) {    // 39 aligned halfwords per plane and round (absent planes and halfwords: 0)
+            const uint32_t hi = i0 / 16u + (uint32_t)lane;
+            const bool ld = lane < kMtN / 16 && hi < 2u * Pw;
+#pragma unroll
+            for (int b = 0; b < 4; ++b)
+                o.pw[b] = (uint16_t)__builtin_amdgcn_raw_buffer_load_b16(rXs, qf_off(ld && (uint32_t)b < nb, ((uint32_t)b * Pw * 2u + hi) * 2u),
+                                                                         0, kAuxNT);
+        } else
 #pragma unroll
         for (int k = 0; k < kMtGroups; ++k) {
             const uint32_t i = i0 + 64u * k + lane;
@@ -1016,10 +1092,18 @@ __device__ __forceinline__ int32_t qfl_recv_rounds(const QflRecvArgs& a, const f
         }
     };
     auto load_m = [&](uint32_t i0, Set& o) {
+        if constexpr (XK == 3) {
+#pragma unroll
+            for (int k = 0; k < kMtGroups; ++k) o.m[k] = 0u;
+        } else
 #pragma unroll
         for (int k = 0; k < kMtGroups; ++k) o.m[k] = __builtin_amdgcn_raw_buffer_load_b8(rmk, i0 + 64u * k + lane, 0, 0);
     };
     auto load_v = [&](uint32_t i0, Set& o) {                     // the round's exact values (0 elsewhere)
+        if constexpr (XK == 3) {
+#pragma unroll
+            for (int k = 0; k < kMtGroups; ++k) o.v[k] = 0.f;
+        } else
 #pragma unroll
         for (int k = 0; k < kMtGroups; ++k) {
             const int e = 64 * k + lane;
@@ -1043,13 +1127,33 @@ __device__ __forceinline__ int32_t qfl_recv_rounds(const QflRecvArgs& a, const f
         if (c + 1 < c1) load_v(i0 + kMtN, nx);
         mt_twist_reg(sL, lane);
         float vv[kMtGroups], qq[kMtGroups];
+        // XK 3: planes 0 | 1 and 2 | 3 side by side; a lane's bits sit in the halfword of lane 4 k + lane / 16
+        int64_t x3[kMtGroups];
+        if constexpr (XK == 3) {
+            const uint32_t p01 = cur.pw[0] | (cur.pw[1] << 16), p23 = cur.pw[2] | (cur.pw[3] << 16);
+#pragma unroll
+            for (int k = 0; k < kMtGroups; ++k) {
+                const int src = (4 * k + (lane >> 4)) & 63, bit = lane & 15;
+                const uint32_t s01 = (uint32_t)__shfl((int)p01, src) >> bit;
+                uint32_t x = (s01 & 1u) | ((s01 >> 15) & 2u);
+                if (nb > 2u) {
+                    const uint32_t s23 = (uint32_t)__shfl((int)p23, src) >> bit;
+                    x |= ((s23 & 1u) << 2) | ((s23 >> 13) & 8u);
+                }
+                x3[k] = (int64_t)x;
+            }
+        }
+        const int64_t(&xs)[kMtGroups] = [&]() -> const int64_t(&)[kMtGroups] {
+            if constexpr (XK == 3) return x3;
+            else return cur.x;
+        }();
 #pragma unroll
         for (int k = 0; k < kMtGroups; ++k) {
             const int e = 64 * k + lane;
             const bool act = e < kMtN && (int64_t)i0 + e < D;
             const uint32_t w = mt_temper(sL[k]);
             const uint32_t h = hpow2 ? (w & (hl - 1u)) : (w % hl);                     // AS:528 randint
-            const int64_t it = (int64_t)((uint64_t)cur.x[k] * (uint64_t)hl + h);       // AS:530 (int64 arithmetic)
+            const int64_t it = (int64_t)((uint64_t)xs[k] * (uint64_t)hl + h);          // AS:530 (int64 arithmetic)
             const bool inr = it >= -(int64_t)tab_n && it < (int64_t)tab_n;
             flags |= (act && !inr) ? UQ_QFL_BAD_INDEX : 0;
             const int32_t idx = inr ? (int32_t)(it < 0 ? it + tab_n : it) : 0;        // take wraps negatives
@@ -1271,6 +1375,116 @@ quicfl_recv_fin_kernel(QflRecvArgs a, QflRunArgs ra) {
     // AS:531 vec[exact_indeces] = exact_values raises unless the counts agree
     if (a.compact && a.exact_count && tot != (int64_t)a.exact_count[j]) flags |= UQ_QFL_BAD_EXACT;
     if (lane == 0 && a.info) a.info[j] = flags;
+}
+
+// ---- the packed message ("Messages at their rate") ---------------------------------
+// payload [n][nbits * P] u32, P = ceil(D / 32): bit i % 32 of word i / 32 of plane b is bit b of X_i,
+// bits that name no coordinate are 0; the exact coordinates as an ascending index row beside the
+// compact values.  The sender's and the receiver's rounds write and read the planes themselves (XK 3
+// above); what follows are the list's kernels and the converters, all plain launches.
+
+// A row's list (count, ascending indices below D), checked by the workgroup: f(t, i) for every entry
+// whose index lies in the row.  True when the list is well formed.
+template <class F>
+__device__ __forceinline__ bool qfl_exact_list(const int32_t* __restrict__ ix, int64_t cnt, int64_t D, F&& f) {
+    bool bad = cnt < 0 || cnt > D;
+    if (!bad)
+        for (int64_t t = threadIdx.x; t < cnt; t += blockDim.x) {
+            const int32_t i = ix[t];
+            const bool inrow = i >= 0 && (int64_t)i < D;
+            bad |= !inrow || (t > 0 && ix[t - 1] >= i);
+            if (inrow) f(t, (int64_t)i);
+        }
+    return !__syncthreads_or(bad);
+}
+
+// The receiver's exact coordinates (AS:531-532), stream-ordered after the rounds and before the
+// inverse RHT: pre[j][exact_index[j][t]] = exact_vals[j][t] / scale[j], the rounds' own division.
+// One workgroup per message; a malformed list flags UQ_QFL_BAD_EXACT and writes nothing outside its row.
+__global__ void __launch_bounds__(256)
+quicfl_exact_scatter_kernel(const int32_t* __restrict__ eidx, const float* __restrict__ ev,
+                            const int32_t* __restrict__ ecount, const float* __restrict__ scale, float* __restrict__ pre,
+                            int32_t* __restrict__ info, int64_t D) {
+    const int64_t j = blockIdx.x, row = j * D;
+    const DivPlan dp = div_plan_norm(scale[j]);
+    const bool ok = qfl_exact_list(eidx + row, ecount[j], D, [&](int64_t t, int64_t i) { pre[row + i] = div1(ev[row + t], dp); });
+    if (!ok && info && threadIdx.x == 0) info[j] |= UQ_QFL_BAD_EXACT;
+}
+
+// X (int64 / uint8 / int32 by x_kind) and the u8 mask -> planes, index row, count, size.  One
+// workgroup per message walks it 256 coordinates at a time: a wave's 64 coordinates are two whole
+// words of each plane (ballots), and the exact coordinates are compacted in index order by ballots
+// and a running count (no atomics).  X outside [0, 2^nbits) is stored as 0 and flags UQ_QFL_X_RANGE;
+// info[j] is written, or ORed into when keep_info is set (behind the u8 sender).
+__global__ void __launch_bounds__(256)
+quicfl_pack_x_kernel(const void* __restrict__ X, int32_t x_kind, int64_t D, int32_t nb, const uint8_t* __restrict__ mask,
+                     uint32_t* __restrict__ payload, int32_t* __restrict__ eidx, int32_t* __restrict__ ecount,
+                     int64_t* __restrict__ payload_bits, int32_t* __restrict__ info, int32_t keep_info) {
+    __shared__ uint32_t wcnt[4];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t j = blockIdx.x, row = j * D;
+    const int64_t P = (D + 31) / 32;
+    uint32_t* pay = payload + j * nb * P;
+    int64_t base = 0;
+    bool range = false;
+    for (int64_t i0 = 0; i0 < D; i0 += 256) {
+        const int64_t i = i0 + threadIdx.x;
+        const bool act = i < D;
+        int64_t xv = 0;
+        if (act) xv = x_kind == 0 ? ((const int64_t*)X)[row + i] : x_kind == 1 ? (int64_t)((const uint8_t*)X)[row + i] : (int64_t)((const int32_t*)X)[row + i];
+        const bool ok = xv >= 0 && xv < ((int64_t)1 << nb);
+        range |= act && !ok;
+        const uint32_t x = ok ? (uint32_t)xv : 0u;
+        const int64_t w = (i0 + 64 * wv) / 32;
+        for (int b = 0; b < nb; ++b) {
+            const uint64_t bal = __ballot(act && ((x >> b) & 1u));
+            if (lane == 0 && w < P) pay[b * P + w] = (uint32_t)bal;
+            if (lane == 0 && w + 1 < P) pay[b * P + w + 1] = (uint32_t)(bal >> 32);
+        }
+        const bool m = act && mask && mask[row + i] != 0;
+        const uint64_t bm = __ballot(m);
+        if (lane == 0) wcnt[wv] = (uint32_t)__popcll(bm);
+        __syncthreads();
+        int64_t before = base;
+        for (int q = 0; q < 4; ++q) {
+            if (q < wv) before += wcnt[q];
+            base += wcnt[q];
+        }
+        if (m) eidx[row + before + __popcll(bm & ((1ull << lane) - 1ull))] = (int32_t)i;
+        __syncthreads();
+    }
+    const bool any = __syncthreads_or(range);
+    if (threadIdx.x == 0) {
+        ecount[j] = (int32_t)base;
+        if (payload_bits) payload_bits[j] = (int64_t)nb * D + 64 * base;
+        if (info) info[j] = (keep_info ? info[j] : 0) | (any ? UQ_QFL_X_RANGE : 0);
+    }
+}
+
+// planes and index row -> u8 X and the u8 mask; info[j] (or null) = UQ_QFL_BAD_EXACT for a malformed list
+__global__ void __launch_bounds__(256)
+quicfl_unpack_x_kernel(const uint32_t* __restrict__ payload, int64_t D, int32_t nb, const int32_t* __restrict__ eidx,
+                       const int32_t* __restrict__ ecount, uint8_t* __restrict__ X, uint8_t* __restrict__ mask,
+                       int32_t* __restrict__ info) {
+    const int64_t j = blockIdx.x, row = j * D;
+    const int64_t P = (D + 31) / 32;
+    const uint32_t* pay = payload + j * nb * P;
+    for (int64_t i = threadIdx.x; i < D; i += 256) {
+        uint32_t x = 0;
+        for (int b = 0; b < nb; ++b) x |= ((pay[b * P + i / 32] >> (i % 32)) & 1u) << b;
+        X[row + i] = (uint8_t)x;
+        mask[row + i] = 0;
+    }
+    __syncthreads();                                     // the row's zeros before its ones
+    const bool ok = !eidx || qfl_exact_list(eidx + row, ecount[j], D, [&](int64_t, int64_t i) { mask[row + i] = 1; });
+    if (info && threadIdx.x == 0) info[j] = ok ? 0 : UQ_QFL_BAD_EXACT;
+}
+
+// info[j] |= extra[j] (the converter path of the receiver: the list's check behind the u8 kernels' flags)
+__global__ void __launch_bounds__(256)
+quicfl_or_info_kernel(int32_t* __restrict__ info, const int32_t* __restrict__ extra, int64_t n) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j < n) info[j] |= extra[j];
 }
 
 }  // namespace

@@ -13,6 +13,9 @@
         $UQDME_QUICFL_TABLES (the reference reads its own tables/ directory).
     quicfl_compress(x[n, d], nbits, seeds, rotation_seeds, sender=...)  -> QuicFLMessages
     quicfl_decompress(X[n, D], nbits, prng_seeds, rotation_seeds, scale[n], dim, recv_table)
+    quicfl_compress(..., packed=True) -> the message at its rate: X bit-packed (nbits planes per row), the
+        exact coordinates as an index list; quicfl_decompress_messages takes either form, quicfl_pack /
+        quicfl_unpack convert on the GPU (include/uq_dme.h has the layout).
 
 Bit-identical to the reference's QuicFLSender.compress (X, exact_indeces, exact_values, scale,
 the global generator's state after the call) on synthetic sender tables
@@ -39,7 +42,8 @@ from ._runtime import as_batch_f32, as_vector_f32, ptr, stream_ptr, workspace_fo
 from .eden import _sign_rows, padded_dim, randomized_inverse_hadamard_transform
 
 __all__ = ["QuicFLReceiver", "QuicFLSender", "QuicFLMessages", "QUICFL_quantize", "quicfl_compress",
-           "quicfl_decompress", "quicfl_decompress_messages", "quicfl_quantize", "prng_seed", "set_tables_prefix"]
+           "quicfl_decompress", "quicfl_decompress_messages", "quicfl_quantize", "quicfl_pack", "quicfl_unpack",
+           "prng_seed", "set_tables_prefix"]
 
 _FLAG_P, _FLAG_INDEX, _FLAG_PX, _FLAG_X, _FLAG_TIMEOUT, _FLAG_EXACT, _FLAG_RECV_INDEX = 1, 2, 4, 8, 16, 32, 64  # UQ_QFL_*
 _tables_prefix = None
@@ -185,6 +189,22 @@ class QuicFLMessages:
     dim: int
     nbits: int
     h_len: int
+    payload: torch.Tensor = None        # int32 [n, nbits * ceil(D / 32)]: X bit-packed in planes (X and exact_mask None)
+    exact_index: torch.Tensor = None    # int32 [n, D]: row j's exact coordinates, ascending, in its first exact_count[j]
+    payload_bits: torch.Tensor = None   # int64 [n]: nbits D + 64 exact_count[j]
+
+    @property
+    def packed(self) -> bool:
+        return self.X is None
+
+    @property
+    def nbytes(self) -> int:
+        """Bytes of X and the exact coordinates as this message holds them: ceil(payload_bits / 8) per message
+        when packed; else X, a mask byte per coordinate and four bytes per exact value."""
+        if self.X is None:
+            return int(((self.payload_bits + 7) // 8).sum().item())
+        n, D = self.X.shape
+        return int(n * D * (self.X.element_size() + 1) + 4 * int(self.exact_count.sum().item()))
 
     def exact_dense(self) -> torch.Tensor:
         """[n, D] f32: each message's exact values at their coordinates, 0 elsewhere.  (In row
@@ -202,7 +222,12 @@ class QuicFLMessages:
         return dense
 
 
-def _raise_send_flags(flags: int) -> None:
+def _packed_words(D: int, nbits: int) -> int:
+    """Words of a message's payload row (uq_quicfl_packed_words): nbits planes of ceil(D / 32)."""
+    return int(nbits) * ((D + 31) // 32)
+
+
+def _raise_send_flags(flags: int, packed: bool = False) -> None:
     if flags & _FLAG_P:
         raise RuntimeError("Expected p_in >= 0 && p_in <= 1 to be true, but got false.")   # AS:484 bernoulli
     if flags & _FLAG_INDEX:
@@ -210,12 +235,12 @@ def _raise_send_flags(flags: int) -> None:
     if flags & _FLAG_PX:
         raise RuntimeError("Expected p_in >= 0 && p_in <= 1 to be true, but got false.")   # AS:489 bernoulli
     if flags & _FLAG_X:
-        raise OverflowError("X outside 0..255: use x_dtype=torch.int64")
+        raise OverflowError("X outside [0, 2^nbits): not a packed message's" if packed else "X outside 0..255: use x_dtype=torch.int64")
     if flags & _FLAG_TIMEOUT:
         raise RuntimeError("uq_quicfl_compress_f32: internal wait ran out (results invalid)")
 
 
-def _send_prologue(x, nbits, seeds, rotation_seeds, sender, px_seeds, px_states, words):
+def _send_prologue(x, nbits, seeds, rotation_seeds, sender, px_seeds, px_states, words, packed=False):
     """What quicfl_compress and quicfl_quantize do before their call: the batch on the device, the
     seeds hashed to prng seeds (AS:457), the small per-message inputs in ONE host-to-device copy
     (the prng seeds in front of the generator states or px seeds, upload_generators), `words` zeroed
@@ -240,7 +265,7 @@ def _send_prologue(x, nbits, seeds, rotation_seeds, sender, px_seeds, px_states,
         tab, rows = _sign_rows(rs, a.D, dev)
         xp = sender.table_xp(nbits, dev)
         tp = sender.table_packed(nbits, dev) if _USE_PACKED else None
-        ws = workspace_for("uq_quicfl_workspace_bytes", dev, n, d)
+        ws = workspace_for("uq_quicfl_packed_workspace_bytes" if packed else "uq_quicfl_workspace_bytes", dev, n, d)
         a.keep = (tab, rows, xp, tp, ws, ps_d, st_in, pxs_d)
         a.head = (ptr(x), n, d, ptr(tab), ptr(rows), ptr(xp), ptr(tp), xp.shape[0], a.h_len,
                   float(np.float32(dd["delta"])))
@@ -250,17 +275,42 @@ def _send_prologue(x, nbits, seeds, rotation_seeds, sender, px_seeds, px_states,
 
 
 def quicfl_compress(x, nbits: int, seeds, rotation_seeds, *, sender: QuicFLSender, px_seeds=None, px_states=None,
-                    x_dtype=torch.uint8, _state_out: bool = False):
+                    x_dtype=torch.uint8, packed: bool = False, _state_out: bool = False):
     """QuicFLSender.compress (AS:455-503) for every row of x [n, d].  seeds: the messages'
     `seed` (hashed to the local generator's seed, AS:457); rotation_seeds: the RHT seeds.
     The bernoulli(p_X) draws (AS:489) of message j come from a fresh generator seeded with
     px_seeds[j], or from px_states[j] ([626] = left, next, state words of a torch CPU
     generator, see generator_words).  X is returned as uint8 (x_dtype=torch.uint8, values
-    outside 0..255 raise) or int64 (the reference's X.long())."""
+    outside 0..255 raise) or int64 (the reference's X.long()).  packed=True: the message at its rate
+    (payload, exact_index, payload_bits; X and exact_mask None), the same bits as quicfl_pack of the uint8
+    message; X outside [0, 2^nbits) raises."""
     if x_dtype not in (torch.uint8, torch.int64):
         raise ValueError("x_dtype must be torch.uint8 or torch.int64")
-    a = _send_prologue(x, nbits, seeds, rotation_seeds, sender, px_seeds, px_states, 2)
+    if packed and x_dtype != torch.uint8:
+        raise ValueError("packed=True holds X in nbits bits: x_dtype=torch.int64 does not apply")
+    a = _send_prologue(x, nbits, seeds, rotation_seeds, sender, px_seeds, px_states, 2, packed)
     n, dev = a.n, a.dev
+    if packed:
+        if not 1 <= int(nbits) <= 4:
+            raise ValueError("packed=True takes nbits 1..4")
+        payload = torch.zeros((n, _packed_words(a.D, nbits)), dtype=torch.int32, device=dev)
+        eidx = torch.empty((n, a.D), dtype=torch.int32, device=dev)
+        pbits = torch.zeros(n, dtype=torch.int64, device=dev)
+        ev = torch.empty((n, a.D), dtype=torch.float32, device=dev)
+        scale = torch.empty(n, dtype=torch.float32, device=dev)
+        hout = np.zeros(a.dout.numel(), np.int32)
+        if n and a.d:
+            _lib.check(_lib.load().uq_quicfl_compress_packed_f32(
+                *a.head, *a.gens, ptr(payload), int(nbits), ptr(eidx), ptr(ev), ptr(a.dout[n:2 * n]), ptr(pbits), ptr(scale),
+                ptr(a.info), *a.tail), "uq_quicfl_compress_packed_f32")
+            hout = a.dout.cpu().numpy()
+            _raise_send_flags(int(np.bitwise_or.reduce(hout[:n])) if n else 0, packed=True)
+        msg = QuicFLMessages(X=None, exact_mask=None, exact_vals=ev, exact_count=torch.from_numpy(hout[n:2 * n].copy()),
+                             scale=scale, prng_seeds=a.ps, rotation_seeds=a.rs, dim=a.d, nbits=nbits, h_len=a.h_len,
+                             payload=payload, exact_index=eidx, payload_bits=pbits)
+        if _state_out:
+            return msg, (hout[2 * n:].reshape(n, STATE_WORDS).view(np.uint32).copy() if a.nst else None)
+        return msg
     X = torch.empty((n, a.D), dtype=x_dtype, device=dev)
     mask = torch.empty((n, a.D), dtype=torch.bool, device=dev)
     ev = torch.empty((n, a.D), dtype=torch.float32, device=dev)
@@ -358,9 +408,90 @@ def _raise_recv_flags(flags: int) -> None:
         raise RuntimeError("shape mismatch: exact_values do not match exact_indeces (AS:531)")
 
 
+def _list_on(msg: QuicFLMessages, dev):
+    """A packed message's rows on the device: payload, exact_index, exact_vals, exact_count."""
+    return (msg.payload.to(dev).contiguous(), msg.exact_index.to(dev).contiguous(), msg.exact_vals.to(dev).contiguous(),
+            torch.as_tensor(msg.exact_count, dtype=torch.int32).reshape(-1).to(dev))
+
+
+def _decompress_packed(msg: QuicFLMessages, recv_table) -> torch.Tensor:
+    dev = _runtime.device()
+    payload, eidx, ev, cnt = _list_on(msg, dev)
+    n, D = payload.shape[0], padded_dim(msg.dim)
+    tab = torch.as_tensor(recv_table, dtype=torch.float32).to(dev).contiguous()
+    rows, hl = (tab.shape[0], tab.shape[1]) if tab.dim() == 2 else (1, tab.numel())
+    if int(msg.h_len) != hl:
+        raise ValueError("h_len does not match the receiver table")
+    if payload.shape[1] != _packed_words(D, msg.nbits) or eidx.shape != (n, D) or ev.shape != (n, D) or cnt.numel() != n:
+        raise ValueError("payload [n, nbits * ceil(D / 32)], exact_index and exact_vals [n, D], exact_count [n]")
+    seeds32 = torch.from_numpy((torch.as_tensor(msg.prng_seeds, dtype=torch.int64).reshape(-1).numpy()
+                                & 0xFFFFFFFF).astype(np.uint32).view(np.int32)).to(dev)
+    rs = torch.as_tensor(msg.rotation_seeds, dtype=torch.int64).reshape(-1)
+    sc = torch.as_tensor(msg.scale, dtype=torch.float32).reshape(-1).to(dev)
+    if seeds32.numel() != n or rs.numel() != n or sc.numel() != n:
+        raise ValueError("one prng seed, rotation seed and scale per message")
+    pre = torch.empty((n, D), dtype=torch.float32, device=dev)
+    info = torch.zeros(n, dtype=torch.int32, device=dev)
+    if n:
+        L = _lib.load()
+        wb = ctypes.c_size_t()
+        _lib.check(L.uq_quicfl_receive_packed_workspace_bytes(n, D, ctypes.byref(wb)), "uq_quicfl_receive_packed_workspace_bytes")
+        ws = torch.empty(max(int(wb.value), 1), dtype=torch.uint8, device=dev)
+        _lib.check(L.uq_quicfl_receive_packed_f32(
+            ptr(payload), int(msg.nbits), n, D, ptr(tab), rows, hl, ptr(seeds32), ptr(eidx), ptr(ev), ptr(cnt), ptr(sc),
+            ptr(pre), ptr(info), ptr(ws), wb.value, stream_ptr(dev)), "uq_quicfl_receive_packed_f32")
+        _raise_recv_flags(int(np.bitwise_or.reduce(info.cpu().numpy())))
+    return randomized_inverse_hadamard_transform(pre, rs)[:, :msg.dim]
+
+
+def quicfl_pack(msg: QuicFLMessages) -> QuicFLMessages:
+    """The packed form of a u8 / int64 message (uq_quicfl_pack_x, on the GPU): what quicfl_compress(...,
+    packed=True) returns for the same input.  A packed message comes back as it is.  X outside
+    [0, 2^nbits) raises OverflowError."""
+    if msg.X is None:
+        return msg
+    dev = _runtime.device()
+    X = msg.X if msg.X.dtype in _X_KIND else msg.X.to(torch.int64)
+    X = X.to(dev).contiguous()
+    n, D = X.shape
+    mask = msg.exact_mask.to(dev).contiguous()
+    payload = torch.zeros((n, _packed_words(D, msg.nbits)), dtype=torch.int32, device=dev)
+    eidx = torch.empty((n, D), dtype=torch.int32, device=dev)
+    cnt = torch.zeros(n, dtype=torch.int32, device=dev)
+    pbits = torch.zeros(n, dtype=torch.int64, device=dev)
+    info = torch.zeros(n, dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().uq_quicfl_pack_x(ptr(X), _X_KIND[X.dtype], n, D, int(msg.nbits), ptr(mask), ptr(payload), ptr(eidx),
+                                             ptr(cnt), ptr(pbits), ptr(info), stream_ptr(dev)), "uq_quicfl_pack_x")
+    _raise_send_flags(int(np.bitwise_or.reduce(info.cpu().numpy())) if n else 0, packed=True)
+    return QuicFLMessages(X=None, exact_mask=None, exact_vals=msg.exact_vals, exact_count=cnt.cpu(), scale=msg.scale,
+                          prng_seeds=msg.prng_seeds, rotation_seeds=msg.rotation_seeds, dim=msg.dim, nbits=msg.nbits,
+                          h_len=msg.h_len, payload=payload, exact_index=eidx, payload_bits=pbits)
+
+
+def quicfl_unpack(msg: QuicFLMessages) -> QuicFLMessages:
+    """The uint8 form of a packed message (uq_quicfl_unpack_x, on the GPU): X and exact_mask as quicfl_compress
+    writes them.  A message that holds X comes back as it is.  A malformed index list raises RuntimeError."""
+    if msg.X is not None:
+        return msg
+    dev = _runtime.device()
+    payload, eidx, _, cnt = _list_on(msg, dev)
+    n, D = payload.shape[0], padded_dim(msg.dim)
+    X = torch.empty((n, D), dtype=torch.uint8, device=dev)
+    mask = torch.empty((n, D), dtype=torch.bool, device=dev)
+    info = torch.zeros(n, dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().uq_quicfl_unpack_x(ptr(payload), n, D, int(msg.nbits), ptr(eidx), ptr(cnt), ptr(X), ptr(mask),
+                                               ptr(info), stream_ptr(dev)), "uq_quicfl_unpack_x")
+    _raise_recv_flags(int(np.bitwise_or.reduce(info.cpu().numpy())) if n else 0)
+    return QuicFLMessages(X=X, exact_mask=mask, exact_vals=msg.exact_vals, exact_count=msg.exact_count, scale=msg.scale,
+                          prng_seeds=msg.prng_seeds, rotation_seeds=msg.rotation_seeds, dim=msg.dim, nbits=msg.nbits,
+                          h_len=msg.h_len)
+
+
 def quicfl_decompress_messages(msg: QuicFLMessages, recv_table) -> torch.Tensor:
     """The receiver (AS:526-535) on every message of a quicfl_compress batch -> [n, dim]
-    (X, mask and the compact exact values read in place)."""
+    (X, mask and the compact exact values read in place; a packed message: its planes and index list)."""
+    if msg.X is None:
+        return _decompress_packed(msg, recv_table)
     return quicfl_decompress(msg.X, msg.nbits, msg.prng_seeds, msg.rotation_seeds, msg.scale, msg.dim, recv_table,
                              msg.h_len, msg.exact_mask, msg.exact_vals, msg.exact_count)
 
