@@ -712,6 +712,40 @@ int uq_eden_decompress_packed_f32(const uint32_t* payload, const float* scale, i
                                   const int8_t* signs, const int32_t* sign_row, const uint32_t* sign_bits,
                                   const uint32_t* mask_bits, const uint32_t* mask_ranks, const int32_t* mask_row, float* out,
                                   void* ws, size_t ws_bytes, void* stream);
+/* The receivers with EDEN's coordinate drop (AS:413-423: `ri = torch.randperm(D)[:round(D * pdrop)];
+ * vec[ri] = 0; vec /= (1 - pdrop)` on the rotated vector, at rates below 1 bit and for the message
+ * field pdrop).  New entry points; the ones above are unchanged and a message without a drop takes
+ * them.  One entry per message form, every rate by `kind` (1, 2, UQ_EDEN_NBITS_FRAC: mask_bits /
+ * mask_row as the _frac entries take them, NULL at 1 and 2 bits):
+ *   drop_bits [n][ceil(D / 32)]: client j's dropped coordinates (uq_randperm_prefix's drop_bits);
+ *   cents: HOST floats, the centroids divided by 1 - pdrop by the caller (the binding divides the
+ *     reference's f32 table with torch itself, so the quotient is the reference's own): the kind's
+ *     table, 2 entries at 1 bit and 4 else (ascending, as AS:309 builds it), then at a fractional
+ *     rate the 1-bit table's two.  The kernels select 0 or a table value; no division runs on the GPU.
+ * uq_eden_decompress_drop_f32: a u8 message; uq_eden_decompress_packed_drop_f32: a packed one (the
+ * payload rows go through uq_eden_unpack_bins' kernel into the workspace's bins); uq_eden_drop_f32:
+ * sender and receiver fused on the workspace's bins, as uq_eden_f32_sb / uq_eden_frac_f32.
+ * Form (uq_test_last_eden_drop_form, this thread's last call of the three): UQ_EDEN_DROP_VECTOR: KE5d
+ * writes the rotated f32 vector [n][D] into the workspace, then the inverse transform's plain passes
+ * and the receiver's last pass run on it (uq_test_last_eden_plan(UQ_EDEN_OP_DECOMPRESS) names them).
+ * No first pass reads the drop rows itself yet; UQ_EDEN_DROP_NONE after a call that launched nothing.
+ * Workspace: uq_eden_workspace_bytes(n, dim).  No host synchronisation. */
+#define UQ_EDEN_DROP_NONE 0
+#define UQ_EDEN_DROP_VECTOR 1
+int uq_test_last_eden_drop_form(int32_t* form_out);
+int uq_eden_decompress_drop_f32(const uint8_t* bins, const float* scale, int64_t n, int64_t dim, int32_t kind,
+                                const int8_t* signs, const int32_t* sign_row, const uint32_t* sign_bits,
+                                const uint32_t* mask_bits, const int32_t* mask_row, const uint32_t* drop_bits,
+                                const float* cents, float* out, void* ws, size_t ws_bytes, void* stream);
+int uq_eden_decompress_packed_drop_f32(const uint32_t* payload, const float* scale, int64_t n, int64_t dim, int32_t kind,
+                                       const int8_t* signs, const int32_t* sign_row, const uint32_t* sign_bits,
+                                       const uint32_t* mask_bits, const uint32_t* mask_ranks, const int32_t* mask_row,
+                                       const uint32_t* drop_bits, const float* cents, float* out, void* ws,
+                                       size_t ws_bytes, void* stream);
+int uq_eden_drop_f32(const float* x, float* out, int64_t n, int64_t dim, int32_t kind, const int8_t* signs,
+                     const int32_t* sign_row, const uint32_t* sign_bits, const uint32_t* mask_bits, const int32_t* mask_row,
+                     const uint32_t* drop_bits, const float* cents, float* scale_out, void* ws, size_t ws_bytes,
+                     void* stream);
 /* torch.norm(v[j], 2) of each row of v [n][D] f32 in torch's CPU order (AS:329: 8 lanes of
  * fma chains, lanes added in order, sqrt), the norm the EDEN entry points use:
  *   mode 1: the sequential chains (one chain per torch lane; what batches above 256 rows use)
@@ -800,6 +834,46 @@ int uq_kashin_f32(const float* x, float* out, int64_t n, int64_t dim, int64_t D,
                   double err, int32_t nlevels, const int8_t* signs, const int32_t* sign_row, const uint32_t* runs,
                   const int32_t* run_row, int64_t run_words, float* mn, float* step, int32_t* info, int32_t* iters,
                   void* ws, size_t ws_bytes, void* stream);
+
+/* ---- torch.randperm(D)[:k] of the CPU generator (EDEN's coordinate drop, All_Schemes.py:419-423) ----
+ * The reference drops round(D * pdrop) coordinates of the rotated vector by
+ * `torch.randperm(D)[:k]` on the global CPU generator.  For D < 2^32 / 20 that is a forward
+ * Fisher-Yates shuffle, step i = 0 .. D - 2 swapping r[i] with r[i + w_i % (D - i)], w_i the
+ * generator's i-th word: D - 1 words whatever k, of which the prefix depends on the first
+ * K = min(k, D - 1).  uq_randperm_prefix computes the prefix of n clients without the serial chain
+ * (csrc/uq_randperm_kernels.h has the algorithm), bit for bit:
+ *   states [n][UQ_QFL_STATE_WORDS] u32 = (left, next, state[624]) of each client's generator where
+ *     its permutation starts (may be NULL when no word is taken: D <= 1 or k = 0).  The generator
+ *     after a permutation is D - 1 words on: the caller advances it (uq_mt_jump_host).
+ *   index_out [n][k] int64 (or NULL) = torch.randperm(D)[:k] per client.
+ *   drop_bits [n][ceil(D / 32)] u32 (or NULL): the same set, coordinate i at bit i % 32 of word
+ *     i / 32 (uq_rht_sign_bits' numbering); the rows are written whole, so every bit that names no
+ *     dropped coordinate, at or above D included, is 0 (k = 0: all of them).
+ * k = 0 writes no index; k = D is the whole permutation (every coordinate dropped); D >= 2^32 / 20
+ * (torch takes another algorithm), k > D and negative sizes return UQ_E_INVALID.
+ * Workspace: uq_randperm_prefix_workspace_bytes(n, D, k), at most about 1 GiB (or one client's
+ * need, 4 (3 k + D) bytes and the jump form's blocks, if that is more); a batch that does not fit
+ * the workspace it is given is processed in groups of clients inside the call, so any size from one
+ * client's up is accepted.  Stream-ordered, no host synchronisation.  The one allocation is the
+ * jump form's table of polynomials, made once per (device, run layout) like QUIC-FL's.
+ * Test hooks: uq_test_last_randperm_plan writes min(cap, UQ_RANDPERM_PLAN_FIELDS) int64 values of
+ * this thread's last call: [0] form of the words stage (UQ_RANDPERM_FORM_*: nothing launched, one
+ * wave per client walks the stream, runs from jumped states, words given by the caller)
+ * [1] runs per client  [2] blocks of 624 words per run  [3] clients per group  [4] K
+ * [5] groups.  uq_test_randperm_from_words runs the same stages on words [n][K] (device) given by
+ * the caller instead of a generator's, for word patterns no generator draws; K <= 65536 there, since
+ * one position's list may then hold every step and each step reads it whole. */
+#define UQ_RANDPERM_PLAN_FIELDS 6
+#define UQ_RANDPERM_FORM_NONE 0
+#define UQ_RANDPERM_FORM_WALK 1
+#define UQ_RANDPERM_FORM_JUMP 2
+#define UQ_RANDPERM_FORM_WORDS 3
+int uq_randperm_prefix_workspace_bytes(int64_t n, int64_t D, int64_t k, size_t* bytes_out);
+int uq_randperm_prefix(const uint32_t* states, int64_t n, int64_t D, int64_t k, int64_t* index_out, uint32_t* drop_bits,
+                       void* ws, size_t ws_bytes, void* stream);
+int uq_test_randperm_from_words(const uint32_t* words, int64_t n, int64_t D, int64_t k, int64_t* index_out,
+                                uint32_t* drop_bits, void* ws, size_t ws_bytes, void* stream);
+int uq_test_last_randperm_plan(int64_t* plan_out, int32_t cap);
 
 /* After the stream has been synchronised: UQ_OK, or UQ_E_TIMEOUT if any
  * inter-workgroup wait in a previous call on this workspace gave up. Clears it. */

@@ -15,13 +15,14 @@ from .quantizer import (
 from .codes import TypeCodes, TypeMessages, encode_messages, decode_messages
 from .biased import Type_biased_quantize, biased_quantize, biased_quantize_encode, biased_quantize_mean
 from .eden import (EDEN_quantize_Hadamard, eden_quantize, eden_compress, eden_decompress, EdenMessage, rht_signs,
-                   randomized_hadamard_transform, randomized_inverse_hadamard_transform, eden_pack, eden_unpack)
+                   randomized_hadamard_transform, randomized_inverse_hadamard_transform, eden_pack, eden_unpack, eden_with_pdrop)
 from .quicfl import (QuicFLReceiver, QuicFLSender, QuicFLMessages, QUICFL_quantize, quicfl_compress,
                      quicfl_decompress, quicfl_decompress_messages, quicfl_quantize, quicfl_pack, quicfl_unpack,
                      set_tables_prefix)
 from .rand_schemes import Scalar_quantize, DRIVE_quantize_Hadamard, scalar_quantize, drive_quantize, drive_words
 from .kashin import (Kashin_quantize, kashin_quantize, kashin_compress, kashin_decompress, kashin_padded_dim,
                      KashinMessage)
+from .randperm import randperm_prefix
 from ._lib import UQError, load as load_library, library_path
 from .distributed import ShardedDME, shard_range, sharded_client_mean, sharded_quantize_mean
 from .dme import DISTRIBUTIONS, Suspended, legacy_draw, nmse_simulation
@@ -43,4 +44,5 @@ __all__ = [
     "eden_compress", "eden_decompress", "eden_pack", "eden_unpack", "EdenMessage", "rht_signs", "randomized_hadamard_transform",
     "randomized_inverse_hadamard_transform", "compute_nmse_stats_auto", "data_format", "round_nmse",
     "DMEPipeline", "codes4_fits", "ShardedDME", "TypeMessages", "encode_messages", "decode_messages", "set_output_pool",
+    "randperm_prefix", "eden_with_pdrop",
 ]

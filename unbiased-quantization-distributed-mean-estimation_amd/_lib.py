@@ -120,6 +120,13 @@ SIGNATURES = {
     # x | payload, scale; n, dim, kind, signs, sign_row, sign_bits, mask_bits, mask_ranks, mask_row, outputs, ws, ws_bytes, stream
     "uq_eden_compress_packed_f32": (ctypes.c_int, [_p, _i64, _i64, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "uq_eden_decompress_packed_f32": (ctypes.c_int, [_p, _p, _i64, _i64, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    # the receivers with the coordinate drop: (bins | payload, scale) | (x, out); n, dim, kind, signs, sign_row, sign_bits,
+    # mask_bits (, mask_ranks), mask_row, drop_bits, cents (host), out | scale_out, ws, ws_bytes, stream
+    "uq_test_last_eden_drop_form": (ctypes.c_int, [_p]),
+    "uq_eden_decompress_drop_f32": (ctypes.c_int, [_p, _p, _i64, _i64, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "uq_eden_decompress_packed_drop_f32": (ctypes.c_int, [_p, _p, _i64, _i64, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,
+                                                          _sz, _p]),
+    "uq_eden_drop_f32": (ctypes.c_int, [_p, _p, _i64, _i64, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "uq_eden_norm_workspace_bytes": (ctypes.c_int, [_i64, _i64, ctypes.POINTER(_sz)]),
     "uq_eden_norm_f32": (ctypes.c_int, [_p, _i64, _i64, _i32, _p, _p, _sz, _p]),
     "uq_rand_workspace_bytes": (ctypes.c_int, [_i64, _i64, ctypes.POINTER(_sz)]),
@@ -140,6 +147,11 @@ SIGNATURES = {
     # iters, ws, ws_bytes, stream
     "uq_kashin_f32": (ctypes.c_int, [_p, _p, _i64, _i64, _i64, _i32, _f64, _f64, _f64, _i32, _p, _p, _p, _p, _i64, _p, _p,
                                      _p, _p, _p, _sz, _p]),
+    # torch.randperm(D)[:k]: states | words, n, D, k, index_out, drop_bits, ws, ws_bytes, stream
+    "uq_randperm_prefix_workspace_bytes": (ctypes.c_int, [_i64, _i64, _i64, ctypes.POINTER(_sz)]),
+    "uq_randperm_prefix": (ctypes.c_int, [_p, _i64, _i64, _i64, _p, _p, _p, _sz, _p]),
+    "uq_test_randperm_from_words": (ctypes.c_int, [_p, _i64, _i64, _i64, _p, _p, _p, _sz, _p]),
+    "uq_test_last_randperm_plan": (ctypes.c_int, [_p, _i32]),
     "uq_tc_bound":(ctypes.c_int, [_i64, ctypes.POINTER(_sz)]),
     "uq_tc_workspace_bytes": (ctypes.c_int, [_i64, _i64, ctypes.POINTER(_sz)]),
     "uq_tc_encode": (ctypes.c_int, [_p, _p, _i64, _i64, _i64, _i32, _p, _sz, _p, _p, _sz, _p]),

@@ -34,13 +34,12 @@ def set_generator_words(gen: torch.Generator, st: np.ndarray, words: np.ndarray)
     gen.set_state(torch.frombuffer(bytearray(b), dtype=torch.uint8).clone())
 
 
-def advance_generator(gen: torch.Generator, nwords: int) -> None:
-    """Leave the CPU generator where `nwords` 32-bit draws leave it -- torch.rand(nwords,
-    generator=gen) on CPU takes one word per f32 element, so this stands for the D bernoulli(p_X)
-    words of AS:489 -- by MT19937 jump-ahead (uq_mt_jump_host) instead of drawing them."""
+def advance_words(w: np.ndarray, nwords: int) -> np.ndarray:
+    """The [626] words of a generator `nwords` 32-bit draws after the state `w` (a new array), by
+    MT19937 jump-ahead (uq_mt_jump_host) instead of drawing them."""
     if nwords < 0:
         raise ValueError("nwords must be >= 0")
-    st, w = generator_words(gen)
+    w = np.array(w, np.uint32)
     left, nxt = int(w[0]), int(w[1])
     rem = left - 1                                   # words left in the current block
     if nwords <= rem:
@@ -54,7 +53,17 @@ def advance_generator(gen: torch.Generator, nwords: int) -> None:
         _lib.check(_lib.load().uq_mt_jump_host(key.ctypes.data, k, out.ctypes.data), "uq_mt_jump_host")
         w[2:] = out
         w[0], w[1] = 625 - r, r
-    set_generator_words(gen, st, w)
+    return w
+
+
+def advance_generator(gen: torch.Generator, nwords: int) -> None:
+    """Leave the CPU generator where `nwords` 32-bit draws leave it -- torch.rand(nwords,
+    generator=gen) on CPU takes one word per f32 element, so this stands for the D bernoulli(p_X)
+    words of AS:489 -- by MT19937 jump-ahead (advance_words) instead of drawing them."""
+    if nwords < 0:
+        raise ValueError("nwords must be >= 0")
+    st, w = generator_words(gen)
+    set_generator_words(gen, st, advance_words(w, nwords))
 
 
 def check_state(words: np.ndarray) -> None:

@@ -539,6 +539,34 @@ int export_packed(const PackedPlan& k, int64_t* out, int32_t cap) {
     return UQ_OK;
 }
 
+// ---- the receiver's coordinate drop (AS:413-423) -------------------------------------------
+thread_local int32_t t_last_drop_form = UQ_EDEN_DROP_NONE;      // uq_test_last_eden_drop_form
+
+// EdenReceiver.decompress with dropped coordinates, the vector form: KE5d writes the rotated vector
+// (0 at a dropped coordinate, else the centroid divided by 1 - pdrop: `cents`, host floats, the
+// kind's own table -- 2 entries at 1 bit, 4 else -- then the 1-bit table's two at a fractional rate)
+// into the workspace's vector buffer; the inverse transform's plain passes and the receiver's last
+// pass (diagonal, scale, [:dim]) follow, as QUIC-FL's receiver runs them.
+int eden_decompress_drop(EdenCall& c, int32_t kind, const float* cents, const uint8_t* bins, const float* scale,
+                         const uint32_t* drop_bits, float* out) {
+    for (int i = 0; i < (kind == 1 ? 2 : 4); ++i) c.tab.c[i] = cents[i];
+    if (c.frac) {
+        c.mask.lo0 = cents[4];
+        c.mask.lo1 = cents[5];
+    }
+    hipStream_t st = (hipStream_t)c.stream;
+    const int64_t D = c.P.D;
+    float* vec = (float*)c.at(c.w.vec_off);
+    const dim3 grid((unsigned)((D + 255) / 256), (unsigned)c.n);
+    if (c.frac) hipLaunchKernelGGL(eden_drop_vec_kernel<true>, grid, dim3(256), 0, st, bins, D, c.tab, c.mask, drop_bits, vec);
+    else hipLaunchKernelGGL(eden_drop_vec_kernel<false>, grid, dim3(256), 0, st, bins, D, c.tab, c.mask, drop_bits, vec);
+    if (const int rc = launched("eden_drop_vec_kernel launch")) return rc;
+    const EdenPlan P = eden_plan(UQ_EDEN_OP_QFL_INVERSE, c.n, D, 0, 0);
+    t_last_plan[UQ_EDEN_OP_DECOMPRESS] = P;              // the passes that ran, under the receiver's hook
+    t_last_drop_form = UQ_EDEN_DROP_VECTOR;
+    return launch_passes(P, fwht_args(vec, c.signs, c.sign_row, c.sbits, scale, D, c.dim, EdenTables{}), c.n, vec, out, st);
+}
+
 }  // namespace
 
 // ---- what QUIC-FL's sender and quantizer run here (uq_internal.h) -------------------------
@@ -825,6 +853,63 @@ int uq_eden_decompress_packed_f32(const uint32_t* payload, const float* scale, i
         uint8_t* bins = (uint8_t*)c.at(c.w.bins_off);
         const int rc = launch_unpack(payload, n, c.P.D, kind, PackRows{mask_bits, mask_ranks, mask_row}, bins, (hipStream_t)stream);
         return rc ? rc : eden_decompress(c, bins, scale, out);
+    });
+}
+
+// ---- the receivers with the coordinate drop (new entry points; the ones above are unchanged) ----
+int uq_test_last_eden_drop_form(int32_t* form_out) {
+    if (!form_out) return fail(UQ_E_INVALID, "null form_out");
+    *form_out = t_last_drop_form;
+    return UQ_OK;
+}
+
+int uq_eden_decompress_drop_f32(const uint8_t* bins, const float* scale, int64_t n, int64_t dim, int32_t kind,
+                                const int8_t* signs, const int32_t* sign_row, const uint32_t* sign_bits,
+                                const uint32_t* mask_bits, const int32_t* mask_row, const uint32_t* drop_bits,
+                                const float* cents, float* out, void* ws, size_t ws_bytes, void* stream) {
+    t_last_plan[UQ_EDEN_OP_DECOMPRESS] = EdenPlan{};
+    t_last_drop_form = UQ_EDEN_DROP_NONE;
+    if (!packed_kind_ok(kind)) return fail(UQ_E_INVALID, "kind must be 1, 2 or UQ_EDEN_NBITS_FRAC");
+    EdenCall c = packed_call(n, dim, kind, signs, sign_row, sign_bits, mask_bits, mask_row, ws, ws_bytes, stream);
+    return eden_call(c, UQ_EDEN_OP_DECOMPRESS, !bins || !scale || !out || !drop_bits || !cents,
+                     [&] { return eden_decompress_drop(c, kind, cents, bins, scale, drop_bits, out); });
+}
+
+int uq_eden_decompress_packed_drop_f32(const uint32_t* payload, const float* scale, int64_t n, int64_t dim, int32_t kind,
+                                       const int8_t* signs, const int32_t* sign_row, const uint32_t* sign_bits,
+                                       const uint32_t* mask_bits, const uint32_t* mask_ranks, const int32_t* mask_row,
+                                       const uint32_t* drop_bits, const float* cents, float* out, void* ws,
+                                       size_t ws_bytes, void* stream) {
+    t_last_plan[UQ_EDEN_OP_DECOMPRESS] = EdenPlan{};
+    t_last_packed[1] = PackedPlan{};
+    t_last_drop_form = UQ_EDEN_DROP_NONE;
+    if (!packed_kind_ok(kind)) return fail(UQ_E_INVALID, "kind must be 1, 2 or UQ_EDEN_NBITS_FRAC");
+    EdenCall c = packed_call(n, dim, kind, signs, sign_row, sign_bits, mask_bits, mask_row, ws, ws_bytes, stream);
+    const bool null_ptr = !payload || !scale || !out || !drop_bits || !cents || (kind == UQ_EDEN_NBITS_FRAC && !mask_ranks);
+    return eden_call(c, UQ_EDEN_OP_DECOMPRESS, null_ptr, [&] {
+        // the payload rows through the converter into the workspace's u8 bins, whatever the kind
+        uint8_t* bins = (uint8_t*)c.at(c.w.bins_off);
+        const int rc = launch_unpack(payload, n, c.P.D, kind, PackRows{mask_bits, mask_ranks, mask_row}, bins, (hipStream_t)stream);
+        return rc ? rc : eden_decompress_drop(c, kind, cents, bins, scale, drop_bits, out);
+    });
+}
+
+int uq_eden_drop_f32(const float* x, float* out, int64_t n, int64_t dim, int32_t kind, const int8_t* signs,
+                     const int32_t* sign_row, const uint32_t* sign_bits, const uint32_t* mask_bits, const int32_t* mask_row,
+                     const uint32_t* drop_bits, const float* cents, float* scale_out, void* ws, size_t ws_bytes,
+                     void* stream) {
+    t_last_plan[UQ_EDEN_OP_DECOMPRESS] = EdenPlan{};
+    t_last_drop_form = UQ_EDEN_DROP_NONE;
+    if (!packed_kind_ok(kind)) return fail(UQ_E_INVALID, "kind must be 1, 2 or UQ_EDEN_NBITS_FRAC");
+    EdenCall c = packed_call(n, dim, kind, signs, sign_row, sign_bits, mask_bits, mask_row, ws, ws_bytes, stream);
+    return eden_call(c, UQ_EDEN_OP_COMPRESS, !x, [&] {
+        uint8_t* bins = (uint8_t*)c.at(c.w.bins_off);
+        float* scale = scale_out ? scale_out : (float*)c.at(c.w.scale_off);
+        const int rc = eden_compress(c, x, bins, scale);
+        if (rc) return rc;
+        if (!out || !drop_bits || !cents) return fail(UQ_E_INVALID, "null pointer");
+        c.P = eden_plan(UQ_EDEN_OP_DECOMPRESS, c.n, c.dim, c.frac ? UQ_EDEN_NBITS_FRAC : c.nbits, 0);
+        return eden_decompress_drop(c, kind, cents, bins, scale, drop_bits, out);
     });
 }
 

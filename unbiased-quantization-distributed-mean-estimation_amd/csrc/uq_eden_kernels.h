@@ -2443,6 +2443,28 @@ eden_unpack_bins_kernel(const uint32_t* __restrict__ payload, int64_t D, PackRow
     }
 }
 
+// ---- the receiver's coordinate drop (AS:413-423) -----------------------------------------------------------------
+// KE5d: the rotated vector of a message with dropped coordinates, vec [n][D] f32: take(centroids, bins) as the
+// receiver's first pass reads it (the table per coordinate by the mask rows when FRAC), with 0 where the client's
+// drop row (uq_randperm_prefix's drop_bits: bit i % 32 of word i / 32) names the coordinate.  The tables the
+// kernel gets hold the centroids divided by 1 - pdrop already (torch's own division, on the host), so
+// `vec[ri] = 0; vec /= (1 - pdrop)` is a select between 0 and a table value.  The inverse transform's plain
+// passes and the receiver's last pass (diagonal, scale, [:dim]) follow on the vector.
+template <bool FRAC>
+__global__ void __launch_bounds__(256)
+eden_drop_vec_kernel(const uint8_t* __restrict__ bins, int64_t D, EdenTables tab, EdenMask mask,
+                     const uint32_t* __restrict__ drop_bits, float* __restrict__ vec) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x, j = blockIdx.y;
+    if (i >= D) return;
+    const EdenCents c = eden_cents(tab);
+    const int b = bins[j * D + i];
+    float v;
+    if (FRAC) v = eden_cent_mixed(c, mask.lo0, mask.lo1, b, mask_bit(mask_row_of(mask, j, D), i));
+    else v = eden_cent(c, b);
+    const uint32_t dropped = (drop_bits[j * ((D + 31) / 32) + (i >> 5)] >> (i & 31)) & 1u;
+    vec[j * D + i] = dropped ? 0.0f : v;
+}
+
 }  // namespace
 
 #endif  // UQ_EDEN_KERNELS_H

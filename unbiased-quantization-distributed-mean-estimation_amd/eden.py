@@ -13,26 +13,35 @@ Batched:
     eden_quantize(x[n, d], bits, seeds[n])              -> out[n, d]
     eden_compress(x[n, d], bits, seeds[n])              -> EdenMessage(bins u8 [n, D], scale[n], seeds, d)
     eden_decompress(msg)                                -> out[n, d]
+    randperm_prefix(D, k, n)                            -> torch.randperm(D)[:k] of the CPU generator (randperm.py)
+
+Coordinate drop (AS:413-423): a message with pdrop > 0 has round(D * pdrop) coordinates of its rotated
+vector zeroed by the receiver (torch.randperm(D) on the global CPU generator, D - 1 words) and the rest
+divided by 1 - pdrop.  The reference's rates below 1 bit are that drop on a 1-bit message:
+EDEN_quantize_Hadamard(v, 1, pdrop=1 - r) is the reference's EDEN_quantize_Hadamard(v, r), bit for bit.
 
 Numerics: rotation (MT19937 diagonal, f32 butterflies a+b / (a+b)-2b, / f32(sqrt(D))), the
 norm (torch CPU order), the bins and the scale (its torch.dot in MKL sdot's order on the fixtures'
 host, oracle/uq_eden.py:torch_dot) are bit-identical to the reference, and with them the outputs.
 Only the 1- and 2-bit tables exist in the reference, so the rates are 1, 2 and what lies between them; a fractional message's nbits is the reference's tuple
-(1, 2, p_high).  Rates below 1 (AS:414-423: the receiver drops coordinates by torch.randperm on the
-global generator) raise ValueError.
+(1, 2, p_high).  The spelling bits_per_dimension < 1 raises ValueError: write bits 1 with pdrop = 1 - bits.
 """
 from __future__ import annotations
 
+import ctypes
+import math
 import threading
 import weakref
 from dataclasses import dataclass
 
+import numpy as np
 import torch
 
-from . import _lib, _runtime
+from . import _lib, _mtstate, _runtime, randperm
 from ._runtime import as_batch_f32, as_vector_f32, ptr, stream_ptr, workspace_for
 
 __all__ = ["EDEN_quantize_Hadamard", "eden_quantize", "eden_compress", "eden_decompress", "eden_pack", "eden_unpack",
+           "eden_drop_form", "eden_with_pdrop",
            "EdenMessage", "eden_mask_bits", "eden_mask_ranks", "packed_words",
            "rht_signs", "padded_dim", "randomized_hadamard_transform", "randomized_inverse_hadamard_transform"]
 
@@ -211,8 +220,46 @@ def _bits(bits):
         return int(b)
     if 1.0 < b < 2.0:
         return (1, 2, b - 1.0)
-    raise ValueError("EDEN supports 1 <= bits <= 2 (the reference's centroid tables, AS:302-306; rates below 1 "
-                     "drop coordinates by torch.randperm on the receiver and are not built)")
+    raise ValueError("EDEN supports 1 <= bits <= 2 (the reference's centroid tables, AS:302-306; a rate r below 1 "
+                     "is the 1-bit message with dropped coordinates: pass bits 1 and pdrop=1 - r)")
+
+
+def _pdrop(pdrop) -> float:
+    """A message's pdrop as a Python float in [0, 1).  (At 1 the reference divides by zero, AS:423.)"""
+    if isinstance(pdrop, (str, bytes)):                  # float() would parse "0.5"; the reference compares numbers
+        raise ValueError("EDEN's pdrop must be a number")
+    try:
+        p = float(pdrop)
+    except (TypeError, ValueError):
+        raise ValueError("EDEN's pdrop must be a number") from None
+    if math.isnan(p) or not 0.0 <= p < 1.0:
+        raise ValueError("EDEN's pdrop must be in [0, 1)")
+    return p
+
+
+# AS:302-309: the centroid tables as the reference builds them (f32 of -c reversed, c)
+_CENTROIDS = {1: [-0.7978845608028654, 0.7978845608028654],
+              2: [-1.5104176087114887, -0.4527800398860679, 0.4527800398860679, 1.5104176087114887]}
+
+
+def _divided_centroids(nb, p: float):
+    """AS:423 `vec /= (1 - pdrop)` on the table instead of the vector: torch's own f32 division of the
+    reference's f32 centroids, as host floats for the drop entry points (the kind's table, then the 1-bit
+    one at a fractional rate)."""
+    t = _CENTROIDS[2] + _CENTROIDS[1] if isinstance(nb, tuple) else _CENTROIDS[nb]
+    q = torch.tensor(t, dtype=torch.float32)
+    q /= (1 - p)
+    return (ctypes.c_float * len(t))(*q.tolist())
+
+
+def _drop_rows(n: int, D: int, p: float, dev, generator, drop_states):
+    """int32 [n, ceil(D / 32)] on the device: the coordinates AS:420-422 drops for each client,
+    torch.randperm(D)[:round(D * p)] of the generator's stream (client j from word j (D - 1); the
+    generator is left n (D - 1) words on, whatever the count) or of drop_states [n, 626]."""
+    k = round(D * p)                                     # AS:421 (Python's round of a float)
+    states = randperm.client_states(n, D, generator, drop_states)
+    sd = torch.from_numpy(states.view(np.int32)).to(dev)
+    return randperm.prefix_from_states(sd, n, D, k, dev, index=False, bits=True)[1]
 
 
 def _threshold(p_high: float) -> int:
@@ -323,6 +370,7 @@ class EdenMessage:
     dim: int
     payload: torch.Tensor = None          # int32 [n, pitch]: the bins bit-packed (include/uq_dme.h has the layout)
     payload_bits: torch.Tensor = None     # int64 [n]: D, 2 D, or D + the client's mask count
+    pdrop: float = 0.0                    # AS:384: the share of coordinates the receiver drops (AS:416-423)
 
     @property
     def packed(self) -> bool:
@@ -386,10 +434,40 @@ def _call_packed(name, dev, seeds, n, d, D, nb, head, tail):
                                             ptr(mr), *map(ptr, tail), ptr(ws), ws.numel(), stream_ptr(dev)), fn)
 
 
+def _call_drop(fn, dev, seeds, n, d, D, nb, head, tail, drop, cents, ranks: bool = False):
+    """uq_eden_decompress_drop_f32 / _packed_drop_f32 / uq_eden_drop_f32(*head, n, d, kind, signs of D, sign rows,
+    sign bits, mask rows (, rank rows), mask row per client, drop rows, divided centroids, *tail, workspace, stream)."""
+    tab, rows, sb = _sign_rows_bits(seeds, D, dev)
+    ws = workspace_for("uq_eden_workspace_bytes", dev, n, d)
+    if ranks:
+        masks = _mask_rows(seeds, D, nb, dev, rows)
+    else:
+        frac = isinstance(nb, tuple)
+        masks = (_mask_table(seeds, D, _threshold(nb[2]), dev), rows) if frac else (None, None)
+    _lib.check(getattr(_lib.load(), fn)(*map(ptr, head), n, d, _kind(nb), ptr(tab), ptr(rows), ptr(sb), *map(ptr, masks),
+                                        ptr(drop), cents, *map(ptr, tail), ptr(ws), ws.numel(), stream_ptr(dev)), fn)
+
+
+def eden_drop_form() -> int:
+    """uq_test_last_eden_drop_form: 0 when this thread's last drop call launched nothing, 1 the vector form."""
+    f = ctypes.c_int32(0)
+    _lib.check(_lib.load().uq_test_last_eden_drop_form(ctypes.byref(f)), "uq_test_last_eden_drop_form")
+    return int(f.value)
+
+
+def eden_with_pdrop(msg: EdenMessage, pdrop: float) -> EdenMessage:
+    """The message with its field pdrop set (AS:384: the sender records data['pdrop'] and does not read it; the
+    receiver drops, AS:416-423): a copy that shares the tensors.  pdrop must be in [0, 1): at 1 the reference
+    divides by zero, and 1, NaN and values outside raise ValueError.  (eden_compress keeps its signature, which
+    the packed form's tests pin, so the field is set on its result.)"""
+    import dataclasses
+    return dataclasses.replace(msg, pdrop=_pdrop(pdrop))
+
+
 def eden_compress(x, bits_per_dimension=1, seeds=None, *, generator=None, packed: bool = False) -> EdenMessage:
     """EdenSender.compress (AS:355-376) for every row of x [n, d].  packed=True: the message at its rate,
     the bins bit-packed into `payload` rows written by the kernels that compute them (bins is None); the
-    same scale, and eden_unpack gives the u8 bins back."""
+    same scale, and eden_unpack gives the u8 bins back.  The message's pdrop is 0: eden_with_pdrop sets it."""
     dev, x, nb, s = _prologue(x, bits_per_dimension, seeds, generator)
     n, d = x.shape
     D = padded_dim(d)
@@ -405,23 +483,41 @@ def eden_compress(x, bits_per_dimension=1, seeds=None, *, generator=None, packed
     return EdenMessage(bins=bins, scale=scale, seeds=s, nbits=nb, dim=d)
 
 
-def eden_decompress(msg: EdenMessage) -> torch.Tensor:
-    """EdenReceiver.decompress (AS:383-413) for every row, of a u8 or a packed message: the same bits."""
+def eden_decompress(msg: EdenMessage, *, generator=None, drop_states=None) -> torch.Tensor:
+    """EdenReceiver.decompress (AS:383-426) for every row, of a u8 or a packed message: the same bits.
+    A message with pdrop > 0 has round(D * pdrop) coordinates of each rotated vector (D: the padded
+    length) zeroed and the rest divided by 1 - pdrop (AS:419-423): client j's coordinates are
+    torch.randperm(D)[:k] of words [j (D - 1), (j + 1)(D - 1)) of `generator` (torch's global CPU
+    generator when None), which is n successive EdenReceiver.decompress calls, and the generator is
+    left n (D - 1) words on, whatever k; drop_states [n, 626] starts each client's permutation from a
+    generator state of its own instead and touches no generator.  pdrop = 0 draws nothing."""
+    p = _pdrop(msg.pdrop)
     dev = _runtime.device()
     scale = msg.scale.to(device=dev, dtype=torch.float32).contiguous()
     d = msg.dim
+    seeds = torch.as_tensor(msg.seeds)
     if msg.bins is None:
         payload = msg.payload.to(dev).contiguous()
         n, D, nb = payload.shape[0], padded_dim(d), _bits(msg.nbits)
         if payload.shape[1] != packed_words(D, nb) or payload.element_size() != 4:
             raise ValueError("a packed EDEN message's payload is [n, packed_words(D, nbits)] 32-bit words")
         out = torch.empty((n, d), dtype=torch.float32, device=dev)
-        _call_packed("decompress", dev, torch.as_tensor(msg.seeds), n, d, D, nb, (payload, scale), (out,))
+        if p > 0 and n and d:
+            drop = _drop_rows(n, D, p, dev, generator, drop_states)
+            _call_drop("uq_eden_decompress_packed_drop_f32", dev, seeds, n, d, D, nb, (payload, scale), (out,), drop,
+                       _divided_centroids(nb, p), ranks=True)
+            return out
+        _call_packed("decompress", dev, seeds, n, d, D, nb, (payload, scale), (out,))
         return out
     bins = msg.bins.to(dev).contiguous()
-    n = bins.shape[0]
+    n, D, nb = bins.shape[0], bins.shape[1], _bits(msg.nbits)
     out = torch.empty((n, d), dtype=torch.float32, device=dev)
-    _call("decompress_f32", dev, torch.as_tensor(msg.seeds), n, d, bins.shape[1], _bits(msg.nbits), (bins, scale), (out,))
+    if p > 0 and n and d:
+        drop = _drop_rows(n, D, p, dev, generator, drop_states)
+        _call_drop("uq_eden_decompress_drop_f32", dev, seeds, n, d, D, nb, (bins, scale), (out,), drop,
+                   _divided_centroids(nb, p))
+        return out
+    _call("decompress_f32", dev, seeds, n, d, D, nb, (bins, scale), (out,))
     return out
 
 
@@ -449,7 +545,7 @@ def eden_pack(msg: EdenMessage) -> EdenMessage:
     pbits = torch.zeros(n, dtype=torch.int64, device=dev)
     _convert("uq_eden_pack_bins", dev, msg, n, D, nb, bins, payload, (pbits,))
     return EdenMessage(bins=None, scale=msg.scale, seeds=msg.seeds, nbits=msg.nbits, dim=msg.dim, payload=payload,
-                       payload_bits=pbits)
+                       payload_bits=pbits, pdrop=msg.pdrop)
 
 
 def eden_unpack(msg: EdenMessage) -> EdenMessage:
@@ -465,16 +561,54 @@ def eden_unpack(msg: EdenMessage) -> EdenMessage:
         raise ValueError("a packed EDEN message's payload is [n, packed_words(D, nbits)] 32-bit words")
     bins = torch.zeros((n, D), dtype=torch.uint8, device=dev)
     _convert("uq_eden_unpack_bins", dev, msg, n, D, nb, payload, bins)
-    return EdenMessage(bins=bins, scale=msg.scale, seeds=msg.seeds, nbits=msg.nbits, dim=msg.dim)
+    return EdenMessage(bins=bins, scale=msg.scale, seeds=msg.seeds, nbits=msg.nbits, dim=msg.dim, pdrop=msg.pdrop)
 
 
-def eden_quantize(x, bits_per_dimension=1, seeds=None, *, return_scale: bool = False, generator=None):
-    """EDEN_quantize_Hadamard for every row of x [n, d] (rotation seed per row)."""
-    dev, x, nb, s = _prologue(x, bits_per_dimension, seeds, generator)
+def _interleaved_draws(n: int, D: int, generator):
+    """n successive reference wrapper calls with a drop on one generator: per client the rotation seed's word
+    (AS:800), then the D - 1 words of its torch.randperm(D) (AS:421) -> (seeds int64 [n], the permutations'
+    start states uint32 [n, 626]); the generator is left where the n calls leave it.  One host jump-ahead per
+    client."""
+    gen = torch.default_generator if generator is None else generator
+    seeds = torch.empty(n, dtype=torch.int64)
+    states = np.empty((n, _mtstate.STATE_WORDS), np.uint32)
+    for j in range(n):
+        seeds[j] = torch.randint(0, _SEEDS, (1,), generator=gen)[0]
+        states[j] = _mtstate.generator_words(gen)[1]
+        _mtstate.advance_generator(gen, randperm.words_taken(D))
+    return seeds, states
+
+
+def eden_quantize(x, bits_per_dimension=1, seeds=None, *, return_scale: bool = False, generator=None, pdrop: float = 0.0,
+                  drop_states=None):
+    """EDEN_quantize_Hadamard for every row of x [n, d] (rotation seed per row).  pdrop in (0, 1): the
+    receiver drops round(D * pdrop) coordinates per row (eden_decompress).  With seeds given, the rows'
+    permutations take n (D - 1) consecutive words of `generator` (drop_states [n, 626]: explicit starts,
+    no generator touched); with seeds=None the call is n successive reference wrapper calls: one seed
+    word, then D - 1 permutation words, per row."""
+    p = _pdrop(pdrop)                                    # (before any draw)
+    if p == 0.0:
+        dev, x, nb, s = _prologue(x, bits_per_dimension, seeds, generator)
+    else:
+        dev = _runtime.device()
+        x = as_batch_f32(x, dev)
+        nb = _bits(bits_per_dimension)
+        if seeds is None and drop_states is not None:
+            raise ValueError("drop_states needs seeds: with seeds=None the rows' draws interleave on one generator")
+        s = _seeds(seeds, x.shape[0]) if seeds is not None else None
     n, d = x.shape
+    D = padded_dim(d)
     out = torch.empty((n, d), dtype=torch.float32, device=dev)
     scale = torch.empty(n, dtype=torch.float32, device=dev)
-    _call("f32", dev, s, n, d, padded_dim(d), nb, (x, out), (scale,))
+    if p > 0 and n and d:
+        if s is None:
+            s, drop_states = _interleaved_draws(n, D, generator)
+        drop = _drop_rows(n, D, p, dev, generator, drop_states)
+        _call_drop("uq_eden_drop_f32", dev, s, n, d, D, nb, (x, out), (scale,), drop, _divided_centroids(nb, p))
+        return (out, scale) if return_scale else out
+    if s is None:
+        s = _seeds(None, n, generator)
+    _call("f32", dev, s, n, d, D, nb, (x, out), (scale,))
     return (out, scale) if return_scale else out
 
 
@@ -508,15 +642,21 @@ def randomized_inverse_hadamard_transform(x, seeds) -> torch.Tensor:
     return _rht(x, seeds, True)
 
 
-def EDEN_quantize_Hadamard(input_vector, bits_per_dimension=1):
+def EDEN_quantize_Hadamard(input_vector, bits_per_dimension=1, pdrop=0.0):
     """Drop-in for AS:792 (same name for the drivers' result keys).  Draws the rotation
     seed from torch's global CPU generator like the CPU reference (AS:797) and returns a
-    NumPy f32 array (AS:811)."""
+    NumPy f32 array (AS:811).  pdrop in [0, 1): the receiver's coordinate drop (AS:413-423), which takes
+    the D - 1 words of torch.randperm(D) from the global generator after the seed's;
+    EDEN_quantize_Hadamard(v, 1, pdrop=1 - r) is the reference's EDEN_quantize_Hadamard(v, r) for a rate
+    r below 1, output and generator state alike (the spelling bits_per_dimension < 1 itself raises
+    ValueError).  At pdrop = 1 the reference divides by zero; here 1, NaN and values outside [0, 1) raise
+    ValueError before any draw."""
+    pdrop = _pdrop(pdrop)
     dev = _runtime.device()
     v = as_vector_f32(input_vector, dev)
     _bits(bits_per_dimension)                            # (a rate without a table raises before the draw)
     seed = int(torch.randint(0, _SEEDS, (1,)).item())
-    out = eden_quantize(v.view(1, -1), bits_per_dimension, seeds=[seed])
+    out = eden_quantize(v.view(1, -1), bits_per_dimension, seeds=[seed], pdrop=pdrop)
     # the NumPy result comes back through pinned memory (torch's caching host allocator):
     # a pageable 4 MB copy costs ~1 ms, about twice the whole GPU work at d = 2^20
     host = torch.empty(out.numel(), dtype=torch.float32, pin_memory=True)
