@@ -94,6 +94,57 @@ def drop_bits(index, D: int) -> np.ndarray:
     return bits
 
 
+WALK, JUMP = 1, 2                 # UQ_RANDPERM_FORM_*
+WALK_BLOCKS = 16                   # streams of up to this many MT19937 blocks: one wave per client walks them
+RUN_BLOCKS = 16                    # jump form: blocks per run at least
+MAX_RUNS = 1024                    # ... and runs per client at most
+RUN_WAVES = 4096                   # ... and about this many run waves per call
+WORKSPACE_CAP = 1 << 30            # uq_randperm_prefix_workspace_bytes asks for no more (one client aside)
+MAX_GROUP = 65535                  # one grid row per client of a group
+JUMP_X = 33 * 624                  # stream words the jump kernel keeps per client
+JUMP_PARTS = 4                     # partial windows per jumped block
+
+
+def plan(n: int, D: int, k: int):
+    """-> (form, runs, run_blocks, K) of the words stage of uq_randperm_prefix(n, D, k) from generator states:
+    the K = min(k, D - 1) words of a stream that may start anywhere in its first block touch B blocks at
+    most; up to 16 blocks one wave walks them (one run of B blocks), else runs of L blocks from jumped
+    states, L = max(16, ceil(B / 1024), min(ceil(n B / 4096), B)).  (0, 0, 0, 0) when nothing runs."""
+    n, D, k = int(n), int(D), int(k)
+    if n < 1 or k < 1:
+        return 0, 0, 0, 0
+    K = min(k, D - 1)
+    B = (624 + K - 1) // 624 + 1
+    if B <= WALK_BLOCKS:
+        return WALK, 1, B, K
+    per = -(-n * B // RUN_WAVES)
+    L = max(RUN_BLOCKS, -(-B // MAX_RUNS), min(per, B))
+    return JUMP, -(-B // L), L, K
+
+
+def workspace_bytes(n: int, D: int, k: int, G: int) -> int:
+    """Bytes of the workspace of a group of G clients under plan(n, D, k): 512 bytes of control block and round
+    flags, then h [G, K], next [G, k], a [G, k], head [G, D] (4-byte entries) and, in the jump form, the stream
+    words [G, 33 * 624] and the partial windows [G, runs, 4, 624]; every array rounded up to 256 bytes."""
+    form, R, _, K = plan(n, D, k)
+    up = lambda b: -(-b // 256) * 256                                 # noqa: E731
+    jump = form == JUMP
+    return 512 + up(G * K * 4) + 2 * up(G * k * 4) + up(G * D * 4) + up(G * JUMP_X * 4 if jump else 0) \
+        + up(G * R * JUMP_PARTS * 624 * 4 if jump else 0)
+
+
+def group(n: int, D: int, k: int, nbytes: int) -> int:
+    """Clients per group of a call with a workspace of `nbytes`: the most whose workspace fits (0: not one)."""
+    lo, hi = 0, min(int(n), MAX_GROUP)
+    while lo < hi:
+        mid = (lo + hi + 1) // 2
+        if workspace_bytes(n, D, k, mid) <= nbytes:
+            lo = mid
+        else:
+            hi = mid - 1
+    return lo
+
+
 def adversarial(kind: str, D: int, K: int) -> np.ndarray:
     """K words whose targets are the hard cases: 'zero' z = 0 (every step hits itself), 'last' every step
     hits position D - 1 (one writer list of length K), 'chain' z_i = 1 but z_{K-1} = 0 (K - 1 links)."""

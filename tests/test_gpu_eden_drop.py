@@ -210,3 +210,55 @@ def test_sub_1_bit_spelling_still_raises(U):
     with pytest.raises(ValueError, match="pdrop=1 - r"):
         U.EDEN_quantize_Hadamard(np.ones(8, np.float32), 0.5)
     assert torch.equal(torch.default_generator.get_state(), before)
+
+
+DROP_STARTS = ((101, 0), (202, 300), (303, 623), (404, 1000))      # freshly seeded, mid-block, next = 623, second block
+
+
+@pytest.mark.parametrize("bits", (1, 1.5))
+def test_batch_whose_permutation_runs_are_set_by_the_batch(U, bits):
+    """n = 3200, d = 16384, pdrop = 0.75: k = 12288 words touch B = 21 blocks and n B / 4096 asks for runs of 17
+    blocks (two runs, the second of 4), where every other test of the drop has runs of 16.  All rows against the
+    same rows in calls of 64 (runs of 16), and sampled rows against the torch path of
+    test_receiver_against_torch_drop_and_the_plain_inverse: centroids from the bins, torch.randperm and the
+    division on the CPU, the GPU's plain inverse.  drop_states tile 4 generator states; seeds are given."""
+    from oracle import uq_eden as E
+    from tests import randperm_model as RM
+    from uqdme_amd import _mtstate, randperm
+    n, d, pdrop = 3200, 16384, 0.75
+    k = round(d * pdrop)
+    rng = np.random.default_rng(16384)
+    x = torch.from_numpy(rng.lognormal(0, 1, (64, d)).astype(np.float32) * rng.choice([-1, 1], (64, d)).astype(np.float32))
+    x = x.cuda().repeat(n // 64, 1)
+    seeds = [int(v) for v in rng.integers(0, 1 << 31, n)]
+    four = np.stack([_mtstate.generator_words(generator(*a))[1] for a in DROP_STARTS])
+    states = four[np.arange(n) % 4]
+    before = torch.default_generator.get_state()
+    big = U.eden_quantize(x, bits, seeds=seeds, pdrop=pdrop, drop_states=states)
+    plan = randperm.last_plan()
+    assert (plan["form"], plan["runs"], plan["run_blocks"], plan["K"]) == RM.plan(n, d, k) == (RM.JUMP, 2, 17, 12288), plan
+    assert plan["group"] * plan["groups"] >= n and plan["group"] == RM.group(n, d, k, RM.WORKSPACE_CAP), plan
+    for c0 in range(0, n, 64):
+        part = U.eden_quantize(x[c0:c0 + 64], bits, seeds=seeds[c0:c0 + 64], pdrop=pdrop, drop_states=states[c0:c0 + 64])
+        assert randperm.last_plan()["run_blocks"] == 16 and randperm.last_plan()["runs"] == 2
+        assert torch.equal(part.view(torch.int32), big[c0:c0 + 64].view(torch.int32)), c0
+    assert torch.equal(torch.default_generator.get_state(), before)
+    rows = {0, 1, 2, 3, 1601, 2046, n - 2, n - 1}                  # every start state among them
+    G0 = plan["group"]
+    if plan["groups"] > 1:                                         # either side of each group boundary
+        rows |= {G0 - 1, G0, (plan["groups"] - 1) * G0 - 1, (plan["groups"] - 1) * G0}
+    for j in sorted(rows):
+        msg = U.eden_with_pdrop(U.eden_compress(x[j:j + 1], bits, seeds=[seeds[j]]), pdrop)
+        bins = msg.bins.cpu().numpy()[0].astype(np.int64)
+        if isinstance(msg.nbits, tuple):
+            m = F.mask(seeds[j], d, msg.nbits[2])
+            vec = np.where(m, E.centroids(2)[bins], E.centroids(1)[np.minimum(bins, 1)]).astype(np.float32)
+        else:
+            vec = E.centroids(msg.nbits)[bins].astype(np.float32)
+        vec = torch.from_numpy(vec)
+        ri = torch.randperm(d, generator=generator(*DROP_STARTS[j % 4]))[:round(d * pdrop)]
+        vec[ri] = 0
+        vec /= (1 - pdrop)
+        inv = U.randomized_inverse_hadamard_transform(vec.view(1, -1), [seeds[j]])
+        want = (msg.scale.to(inv.device).view(1, 1) * inv)[:, :d]
+        assert torch.equal(big[j:j + 1].view(torch.int32), want.view(torch.int32)), j

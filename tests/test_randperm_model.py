@@ -87,3 +87,53 @@ def test_parallel_model_on_random_words():
 def test_drop_bits_numbering():
     bits = M.drop_bits([0, 31, 32, 70], 71)
     assert bits.tolist() == [0x80000001, 1, 1 << 6]
+
+
+PLAN_TABLE = (
+    # n, D, k -> form, runs R, run blocks L
+    ((3, 20000, 20000), (M.JUMP, 3, 16)),
+    ((2500, 20000, 20000), (M.JUMP, 2, 21)),            # L set by the batch, a last run of 13 blocks
+    ((4096, 20000, 20000), (M.JUMP, 1, 34)),            # L = B: one run, no jump taken
+    ((5000, 20000, 10000), (M.JUMP, 1, 18)),
+    ((1300, 65536, 32768), (M.JUMP, 3, 18)),
+    ((128, 1 << 20, 1 << 19), (M.JUMP, 32, 27)),
+    ((128, 1 << 20, 1 << 20), (M.JUMP, 32, 53)),
+    ((1, 10_223_000, 10_223_000), (M.JUMP, 964, 17)),   # B = 16385: L set by the 1024 runs a client may have
+    ((1, 10_222_000, 10_222_000), (M.JUMP, 1024, 16)),  # B = 16383: 1024 runs of 16, the last of 15 blocks
+)
+
+
+@pytest.mark.parametrize("args,want", PLAN_TABLE)
+def test_plan_table(args, want):
+    n, D, k = args
+    form, R, L, K = M.plan(n, D, k)
+    assert (form, R, L) == want and K == min(k, D - 1)
+    B = (624 + K - 1) // 624 + 1
+    assert (R - 1) * L < B <= R * L                                   # the runs cover the blocks, none is empty
+
+
+def test_plan_walk_form_and_empty_calls():
+    assert M.plan(1, 9361, 9361) == (M.WALK, 1, 16, 9360)
+    assert M.plan(7, 9362, 9362) == (M.JUMP, 2, 16, 9361)
+    assert M.plan(5000, 65536, 9360) == (M.WALK, 1, 16, 9360)         # the walk form whatever the batch
+    assert M.plan(1, 2, 2) == (M.WALK, 1, 2, 1) and M.plan(1, 1, 1) == (M.WALK, 1, 1, 0)
+    assert M.plan(0, 100, 10) == (0, 0, 0, 0) and M.plan(3, 100, 0) == (0, 0, 0, 0)
+    # the 1024-run limit takes over between B = 16384 and 16385 blocks: K = 10 222 992 and 10 222 993 words
+    assert M.plan(1, 10_222_993, 10_222_993)[:3] == (M.JUMP, 1024, 16)
+    assert M.plan(1, 10_222_994, 10_222_994)[:3] == (M.JUMP, 964, 17)
+
+
+def test_workspace_model_matches_the_library():
+    """tests/randperm_model.py's workspace_bytes and group against uq_randperm_prefix_workspace_bytes (host code):
+    a batch below the 1 GiB cap asks for its n clients' worth, one above for its largest group's."""
+    import ctypes
+
+    import uqdme
+    lib = uqdme.load_library()
+    b = ctypes.c_size_t(0)
+    for (n, D, k), _ in PLAN_TABLE + (((5, 1000, 1000), None), ((40, 20000, 20000), None), ((128, 1 << 22, 1 << 22), None)):
+        assert lib.uq_randperm_prefix_workspace_bytes(n, D, k, ctypes.byref(b)) == 0
+        G = max(1, M.group(n, D, k, M.WORKSPACE_CAP))
+        assert b.value == M.workspace_bytes(n, D, k, G), (n, D, k)
+        assert G == n or M.workspace_bytes(n, D, k, G + 1) > M.WORKSPACE_CAP
+        assert M.group(n, D, k, b.value) == G and M.group(n, D, k, M.workspace_bytes(n, D, k, 1) - 1) == 0

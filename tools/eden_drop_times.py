@@ -98,10 +98,21 @@ def main():
                "pdrop0_ms": median_ms(lambda: uqdme.eden_quantize(x, 1, seeds=seeds), a.reps, a.warmup),
                "host_jumps_ms": median_ms(lambda: randperm.client_states(n, d, generator=g), a.reps, a.warmup),
                "host_ms_per_client": res["randperm_prefix"].get(f"D={d}/k={d // 2}", {}).get("host_ms")}
+        t = torch.Generator()
+        t.set_state(g.get_state())
         sd = torch.from_numpy(randperm.client_states(n, d, generator=g).view(np.int32)).to(dev)
         row["drop_rows_device_ms"] = event_ms(
             lambda: randperm.prefix_from_states(sd, n, d, d // 2, dev, index=False, bits=True), a.reps, a.warmup)
         row["plan"] = randperm.last_plan()
+        # what was timed is checked: the index rows of the first and the last client against torch.randperm
+        idx = randperm.prefix_from_states(sd, n, d, d // 2, dev)[0]
+        for j in range(n):
+            ref = torch.randperm(d, generator=t)
+            if j in (0, n - 1) and not torch.equal(idx[j].cpu(), ref[:d // 2]):
+                raise SystemExit(f"batch {n} x {d}: client {j}'s permutation differs from torch.randperm")
+        if not torch.equal(t.get_state(), g.get_state()):
+            raise SystemExit(f"batch {n} x {d}: the generator is not where {n} torch.randperm calls leave it")
+        row["checked_clients"] = [0, n - 1]
         res["batch"][f"{n}x{d}"] = row
         print(n, d, row, flush=True)
     txt = json.dumps(res, indent=1)
